@@ -6,7 +6,7 @@ The same run also measures BASELINE config 2 / 4 (bs=512/GPU, the north star's r
 ``sub_configs.dc_gan_bs512`` -- on one GPU and, with ``--gpus N``, on all N ranks -- and, on one GPU, config 3
 (wgan_gp bs 256), config 5's per-GPU workload (hologan bs 64, at 64x64 and as EXT-128) and wgan bs 512.
 
-    python bench.py [--gpus N --steps K --warmup W --batch B]
+    python bench.py [--gpus N --steps K --warmup W --batch B --dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" is one G+D pair: training_step(optimizer_idx=0)+backward+Adam on one batch of B reals,
@@ -15,8 +15,13 @@ counts both batches (2*B*N / t_pair).  Prints ONE JSON line on rank 0.
 
 ``--gpus N`` with N > 1 and no torch.distributed environment: this process only spawns the N ranks
 (``python -m torch.distributed.run``, before anything here touches a GPU) and relays their line.
-The timed region is K pairs bracketed by barrier + synchronize, repeated ``--reps`` times (default 3);
-``ms_per_step`` / ``value`` are the MEDIAN repetition (max over ranks inside each).
+The timed region is K pairs bracketed by barrier + synchronize (max over ranks): ``--steps`` is the number of timed
+steps.  ``--reps R`` repeats the region R times (default 1) and reports the MEDIAN repetition as ``ms_per_step`` /
+``value``.
+
+``--dump-outputs DIR`` writes what the headline's timed path computed in its last step (see dump_outputs) as
+``DIR/<name>.npy``; with the same arguments the inputs are the same from run to run (seeded weights, data and noise),
+so two builds can be compared output for output.
 """
 import argparse
 import gc
@@ -58,7 +63,9 @@ GRADSYNC_W1_CONFIGS = ("dc_gan_bs128", "dc_gan_bs512", "wgan_gp_bs256", "hologan
 DEFAULT_BATCH = {"dc_gan": 128, "wgan": 512, "wgan_gp": 256, "hologan": 64, "gan_stability_r1": 64}
 PEAK_FP32_MFMA_TFLOPS = 157.3             # MI355X_MICROARCH.md: v_mfma_f32_32x32x2_f32, 256 CU x 256 FLOP/clk x 2.4 GHz
 OVERLAP_CYCLES = 4  # untimed cycles behind a timed region in which ddp.GradSync brackets its bucket waits with events
-TIMER_EVERY = 4     # per-launch HIP events on every 4th cycle of the timed region (they cost ~5 % when always on)
+TIMER_EVERY = 4     # per-launch HIP events on one cycle in 4 of the timed region's count, run in untimed cycles of
+                    # their own just before it (two event records per launch cost ~5 % of a step)
+DUMP_LIMIT_BYTES = 64_000_000  # --dump-outputs: at most this much in all (larger tensors keep a seeded sample)
 
 
 def parse_args(argv=None):
@@ -66,7 +73,8 @@ def parse_args(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--reps", type=int, default=3, help="repetitions of the K-step timed region; the median is reported")
+    ap.add_argument("--reps", type=int, default=1,
+                    help="repetitions of the K-step timed region (the median is reported); 1 = K timed steps in all")
     ap.add_argument("--batch", type=int, default=None,
                     help="per-GPU batch (default: BASELINE's: dc_gan 128 = the metric string, wgan_gp 256, hologan 64)")
     ap.add_argument("--expt", default="dc_gan")
@@ -88,7 +96,11 @@ def parse_args(argv=None):
                     help="skip the single-rank-RCCL GradSync sub-records of the default run")
     ap.add_argument("--force-grad-sync", action="store_true",
                     help="use the data-parallel gradient path (flat buffers, deferred step) even on one rank")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the headline's last timed step's outputs (losses, trained state) as DIR/<name>.npy")
     args = ap.parse_args(argv)
+    if args.steps < 1 or args.reps < 1:
+        ap.error("--steps and --reps must be at least 1")
     if args.batch is None:
         args.batch = DEFAULT_BATCH.get(args.expt, 128)
     if args.img_size is None:
@@ -137,13 +149,12 @@ def synthetic_batch(batch, device, rank, img_size=64):
     return real, torch.zeros(batch, dtype=torch.int64, device=device)
 
 
-def timed_pairs(trainer, batch, steps, warmup, world, timer=None, reps=1, on_timed_start=None):
-    """-> (per-repetition seconds for ``steps`` cycles, max over ranks; per-rank seconds of the median repetition)."""
+def timed_pairs(trainer, batch, steps, warmup, world, reps=1, on_timed_start=None):
+    """-> (per-repetition seconds for ``steps`` cycles, max over ranks; per-rank seconds of the median repetition;
+    seconds of the median repetition; what ``trainer.step`` returned for each batch of the last timed cycle)."""
     import torch
     import torch.distributed as dist
     per_pair = len(trainer.order)         # batches per optimizer cycle (2 for dc_gan)
-    if timer is not None:
-        timer.enabled = False
     for _ in range(warmup * per_pair):
         trainer.step(batch)
     trainer.finish()
@@ -157,15 +168,14 @@ def timed_pairs(trainer, batch, steps, warmup, world, timer=None, reps=1, on_tim
     if on_timed_start is not None:
         on_timed_start()
     times, per_rank = [], []
+    last = [None] * per_pair
     for rep in range(reps):
         if world > 1:
             dist.barrier()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         for i in range(steps * per_pair):
-            if timer is not None:
-                timer.enabled = rep == 0 and (i // per_pair) % TIMER_EVERY == 0
-            trainer.step(batch)
+            last[i % per_pair] = trainer.step(batch)
         trainer.finish()
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
@@ -182,7 +192,7 @@ def timed_pairs(trainer, batch, steps, warmup, world, timer=None, reps=1, on_tim
         times.append(dt)
         per_rank.append(ranks)
     med = sorted(range(reps), key=lambda r: times[r])[reps // 2]
-    return times, per_rank[med], times[med]
+    return times, per_rank[med], times[med], last
 
 
 def cpu_baseline(batch=128, budget_s=20.0):
@@ -270,7 +280,7 @@ def roofline_of(timer, ms_per_step, steps, flop_cycle, config_key=None):
     agg = timer.summary()
     if not agg:
         return None
-    sampled_cycles = (steps + TIMER_EVERY - 1) // TIMER_EVERY      # cycles 0, 4, 8, ... of the first repetition
+    sampled_cycles = (steps + TIMER_EVERY - 1) // TIMER_EVERY      # the untimed cycles before the timed region
     total_ms = sum(v[1] for v in agg.values())
     label, (n, ms, fl) = max(agg.items(), key=lambda kv: kv[1][1])
     achieved = fl / (ms * 1e-3) / 1e12
@@ -307,12 +317,40 @@ def config_key_of(expt, batch, img_size):
     return "%s_bs%d_%d" % (expt, batch, img_size)
 
 
+def dump_outputs(out_dir, module, last):
+    """What the timed path handed its caller in the last timed optimizer cycle, as ``out_dir/<name>.npy``:
+    ``losses`` (float64, the loss ``trainer.step`` returned for each batch of the cycle, in order) and the trained
+    module's state after the cycle, one file per ``state_dict`` entry (``generator.*``, ``discriminator.*``: parameters
+    in float32, integer buffers in float64).  Over DUMP_LIMIT_BYTES in all, each state entry keeps the same fraction of
+    its elements, chosen by a generator seeded with the entry's name: the sample is the same in every run."""
+    import zlib
+
+    import numpy as np
+    arrays = {"losses": np.array([float(loss) for loss, _ in last], dtype=np.float64)}
+    for name, t in module.state_dict().items():
+        t = t.detach().cpu()
+        arrays[name] = t.numpy().astype(np.float32 if t.is_floating_point() else np.float64).reshape(-1)
+    total = sum(a.nbytes for a in arrays.values())
+    keep = min(1.0, (DUMP_LIMIT_BYTES - 256 * len(arrays)) / total)     # 256 bytes: room for each .npy header
+    sampled = keep < 1.0
+    os.makedirs(out_dir, exist_ok=True)
+    written = 0
+    for name, a in arrays.items():
+        if sampled and name != "losses" and a.size > 1:
+            rng = np.random.default_rng(zlib.crc32(name.encode()))
+            a = a[np.sort(rng.choice(a.size, max(1, int(a.size * keep)), replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        written += os.path.getsize(os.path.join(out_dir, name + ".npy"))
+    return {"dir": os.path.abspath(out_dir), "files": len(arrays), "bytes": written, "sampled": sampled}
+
+
 def measure(F, expt, batch, img_size, device, rank, world, steps, warmup, reps, use_timer, force_sync=False,
-            graph=False):
+            graph=False, dump_dir=None):
     """One configuration, timed as the contract says: ``warmup`` untimed cycles, then ``reps`` regions of exactly
     ``steps`` optimizer cycles, each bracketed by barrier + synchronize, max over ranks, the median region reported;
-    per-launch HIP events on the launch stream (every 4th cycle of the first region) give the roofline of the dominant
-    kernel.  With world > 1 the trainer carries the gradient exchange (ddp.GradSync) and the record its overlap."""
+    per-launch HIP events on the launch stream (ceil(steps / TIMER_EVERY) untimed cycles between the warm-up and the
+    timed regions) give the roofline of the dominant kernel.  With world > 1 the trainer carries the gradient exchange (ddp.GradSync) and the record its overlap.
+    ``dump_dir``: rank 0 writes the last timed cycle's outputs there (dump_outputs) before anything else runs."""
     import torch
     module, trainer = build_trainer(expt, batch, device, world, force_sync, img_size, graph)
     data = synthetic_batch(batch, device, rank, img_size)
@@ -320,8 +358,6 @@ def measure(F, expt, batch, img_size, device, rank, world, steps, warmup, reps, 
     for _ in range(8 if graph else 2):          # graph mode: eager warm-up + capture of both optimizer steps
         trainer.step(data)
     trainer.finish()
-    if use_timer and not graph:                 # per-launch events cannot be recorded inside a replayed graph
-        F.set_kernel_timer(timer)
     sync = getattr(trainer, "grad_sync", None)
     # the overlap report brackets every wait for a gradient bucket with two timing events on the compute stream -- two
     # more marker packets per bucket, each a ~10-20 us bubble: it is collected in OVERLAP_CYCLES extra cycles behind
@@ -329,9 +365,20 @@ def measure(F, expt, batch, img_size, device, rank, world, steps, warmup, reps, 
     want_overlap = sync is not None and sync.measure
     if want_overlap:
         sync.measure = False
-    times, per_rank, dt = timed_pairs(trainer, data, steps, warmup, world, timer, reps)
-    F.set_kernel_timer(None)
+
+    def sample_kernels():
+        F.set_kernel_timer(timer)
+        for _ in range((steps + TIMER_EVERY - 1) // TIMER_EVERY * len(trainer.order)):
+            trainer.step(data)
+        trainer.finish()
+        torch.cuda.synchronize()
+        F.set_kernel_timer(None)
+
+    # per-launch events cannot be recorded inside a replayed graph
+    sample = sample_kernels if use_timer and not graph else None
+    times, per_rank, dt, last = timed_pairs(trainer, data, steps, warmup, world, reps, on_timed_start=sample)
     torch.cuda.synchronize()
+    dumped = dump_outputs(dump_dir, module, last) if dump_dir is not None and rank == 0 else None
     overlap_cycles = 0
     if want_overlap:
         sync.measure = True
@@ -351,6 +398,8 @@ def measure(F, expt, batch, img_size, device, rank, world, steps, warmup, reps, 
            "n_gpus": world, "steps": steps, "batches_per_step": per_cycle,
            "ms_per_step_each": [round(t / steps * 1e3, 3) for t in times],
            "per_rank_ms_per_step": [round(t / steps * 1e3, 3) for t in per_rank]}
+    if dumped is not None:
+        rec["dumped_outputs"] = dumped
     if sync is not None:
         rec["grad_exchange"] = {"buckets": [[(e - s0) * 4 for s0, e, _, _ in fg.buckets] for fg in sync.flats],
                                 "deferred_tail_buckets": [sorted(fg.tail_buckets) for fg in sync.flats],
@@ -371,11 +420,8 @@ def measure(F, expt, batch, img_size, device, rank, world, steps, warmup, reps, 
             rec["grad_exchange"]["cu_budget"] = sync.cu_budget
     fl = flop_per_cycle(expt, batch, img_size)
     if rank == 0:
-        roof = roofline_of(timer, times[0] / steps * 1e3, steps, fl, config_key_of(expt, batch, img_size))
+        roof = roofline_of(timer, ms, steps, fl, config_key_of(expt, batch, img_size))
         if roof is not None:
-            if roof["whole_step"] is not None:      # the whole step is priced on the reported (median) time
-                a = fl / (ms * 1e-3) / 1e12
-                roof["whole_step"].update(achieved=round(a, 2), frac=round(a / PEAK_FP32_MFMA_TFLOPS, 4))
             rec["roofline"] = roof
         elif fl == fl:
             a = fl / (ms * 1e-3) / 1e12
@@ -562,10 +608,10 @@ def run_rank(args):
     if args.force_grad_sync and world == 1:       # the headline itself on the data-parallel code path (profiling runs)
         with single_rank_rccl(device):
             head = measure(F, args.expt, args.batch, args.img_size, device, rank, world, args.steps, args.warmup,
-                           args.reps, use_timer, True, args.graph)
+                           args.reps, use_timer, True, args.graph, args.dump_outputs)
     else:
         head = measure(F, args.expt, args.batch, args.img_size, device, rank, world, args.steps, args.warmup, args.reps,
-                       use_timer, args.force_grad_sync, args.graph)
+                       use_timer, args.force_grad_sync, args.graph, args.dump_outputs)
     head_key = config_key_of(args.expt, args.batch, args.img_size)
 
     out = {
@@ -595,6 +641,8 @@ def run_rank(args):
         out["grad_exchange"] = head["grad_exchange"]
     if "roofline" in head:
         out["roofline"] = head["roofline"]
+    if "dumped_outputs" in head:
+        out["dumped_outputs"] = head["dumped_outputs"]
 
     default_run = args.expt == "dc_gan" and args.img_size == 64 and not args.no_bs128
     if default_run:
