@@ -2,11 +2,15 @@
 """Headline benchmark: images/sec of the DCGAN G+D training step (64x64, synthetic data, fp32, bs=128/GPU --
 the batch BASELINE.json's metric string names) on N MI355X GPUs of one node, through the reference's own surface
 (training_step / backward / optimizer.step with Lightning's per-batch optimizer alternation and toggle).
-The same run also measures BASELINE config 2 / 4 (bs=512/GPU, the north star's roofline batch) as
-``sub_configs.dc_gan_bs512`` -- on one GPU and, with ``--gpus N``, on all N ranks -- and, on one GPU, config 3
-(wgan_gp bs 256), config 5's per-GPU workload (hologan bs 64, at 64x64 and as EXT-128) and wgan bs 512.
 
-    python bench.py [--gpus N --steps K --warmup W --batch B --dump-outputs DIR]
+A plain run does only what the headline needs: set up, warm up, time the K steps, write --dump-outputs, print the line.
+``--full`` adds everything else: the per-launch kernel roofline of the headline, the gradient-exchange overlap report
+(N > 1), BASELINE config 2 / 4 (bs=512/GPU, the north star's roofline batch) as ``sub_configs.dc_gan_bs512`` -- on one
+GPU and, with ``--gpus N``, on all N ranks -- and, on one GPU, config 3 (wgan_gp bs 256), config 5's per-GPU workload
+(hologan bs 64, at 64x64 and as EXT-128), wgan bs 512, the single-rank-RCCL GradSync records, the FID@50k feature pass
+and the CPU baseline.  The headline figure and the dumped outputs are the same with and without ``--full``.
+
+    python bench.py [--gpus N --steps K --warmup W --batch B --dump-outputs DIR --full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" is one G+D pair: training_step(optimizer_idx=0)+backward+Adam on one batch of B reals,
@@ -49,7 +53,7 @@ FLOP_PER_SAMPLE_CYCLE = {
 # extension, tests/diagnostics/flop_trace.py hologan 128 -> D step 11.4411 G + 2 x G step 13.7115 G
 FLOP_PER_SAMPLE_CYCLE_EXT128 = {"hologan": 38_864_160_640}
 NATIVE_IMG_SIZE = {"gan_stability_r1": 128}
-# BASELINE.json configs measured in the default run next to the headline (the metric string's dc_gan bs 128 / GPU):
+# BASELINE.json configs measured in a --full run next to the headline (the metric string's dc_gan bs 128 / GPU):
 # configs[1] / [3] = dc_gan bs 512 / GPU (every world size), and on one GPU config 3 (wgan_gp bs 256), config 5's
 # per-GPU workload (hologan bs 64, at the parity-pinned 64x64 and as EXT-128) and the 5 : 1 wgan cycle
 SUB_CONFIGS = (("dc_gan_bs128", "dc_gan", 128, 64), ("dc_gan_bs512", "dc_gan", 512, 64),
@@ -58,7 +62,7 @@ SUB_CONFIGS = (("dc_gan_bs128", "dc_gan", 128, 64), ("dc_gan_bs512", "dc_gan", 5
 # what a --gpus N run times on all ranks: the metric's batch, BASELINE config 4 (dc_gan bs 512 / GPU) and config 5
 # (hologan 128x128 bs 64 / GPU: EXT-128, throughput only -- the reference cannot run at 128)
 MULTI_GPU_SUB_CONFIGS = ("dc_gan_bs128", "dc_gan_bs512", "hologan_ext128_bs64")
-# the data-parallel code path on ONE GPU (single-rank RCCL), timed next to the plain trainer in every default run
+# the data-parallel code path on ONE GPU (single-rank RCCL), timed next to the plain trainer in every --full run
 GRADSYNC_W1_CONFIGS = ("dc_gan_bs128", "dc_gan_bs512", "wgan_gp_bs256", "hologan_ext128_bs64")
 DEFAULT_BATCH = {"dc_gan": 128, "wgan": 512, "wgan_gp": 256, "hologan": 64, "gan_stability_r1": 64}
 PEAK_FP32_MFMA_TFLOPS = 157.3             # MI355X_MICROARCH.md: v_mfma_f32_32x32x2_f32, 256 CU x 256 FLOP/clk x 2.4 GHz
@@ -80,20 +84,25 @@ def parse_args(argv=None):
     ap.add_argument("--expt", default="dc_gan")
     ap.add_argument("--img-size", type=int, default=None,
                     help="default 64 (128 for gan_stability_r1); 128 with --expt hologan is EXT-128, not parity-pinned")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: kernel roofline, gradient-exchange overlap, the "
+                         "other configurations (sub_configs), the CPU baseline; the --no-* options below trim it")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-bs128", "--no-sub-configs", dest="no_bs128", action="store_true",
-                    help="headline configuration only (skip the dc_gan bs128 / wgan_gp / hologan sub-records)")
+                    help="--full: headline configuration only (skip the dc_gan bs128 / wgan_gp / hologan sub-records)")
     ap.add_argument("--sub-steps", type=int, default=10, help="timed optimizer cycles per repetition of a sub-record")
-    ap.add_argument("--no-kernel-timer", action="store_true")
+    ap.add_argument("--no-kernel-timer", action="store_true",
+                    help="skip the untimed cycles between the warm-up and the timed region (--full: and the roofline "
+                         "of the kernels timed in them)")
     ap.add_argument("--detail", action="store_true",
-                    help="full sub-configuration records (per-label igemm tables, bucket layouts); the default line keeps "
+                    help="full sub-configuration records (per-label igemm tables, bucket layouts); a --full line keeps "
                          "them to their numbers so that the whole line fits the ~8 KB of stdout a driver record keeps")
     ap.add_argument("--graph", action="store_true",
                     help="replay each optimizer step from a captured HIP graph (single GPU)")
     ap.add_argument("--fid-samples", type=int, default=50000,
-                    help="images of the FID feature pass sub-record (sub_configs.fid50k_features); 0 skips it")
+                    help="images of the FID feature pass sub-record of --full (sub_configs.fid50k_features); 0 skips it")
     ap.add_argument("--no-gradsync-w1", action="store_true",
-                    help="skip the single-rank-RCCL GradSync sub-records of the default run")
+                    help="skip the single-rank-RCCL GradSync sub-records of --full")
     ap.add_argument("--force-grad-sync", action="store_true",
                     help="use the data-parallel gradient path (flat buffers, deferred step) even on one rank")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
@@ -345,12 +354,15 @@ def dump_outputs(out_dir, module, last):
 
 
 def measure(F, expt, batch, img_size, device, rank, world, steps, warmup, reps, use_timer, force_sync=False,
-            graph=False, dump_dir=None):
+            graph=False, dump_dir=None, full=True):
     """One configuration, timed as the contract says: ``warmup`` untimed cycles, then ``reps`` regions of exactly
     ``steps`` optimizer cycles, each bracketed by barrier + synchronize, max over ranks, the median region reported;
     per-launch HIP events on the launch stream (ceil(steps / TIMER_EVERY) untimed cycles between the warm-up and the
     timed regions) give the roofline of the dominant kernel.  With world > 1 the trainer carries the gradient exchange (ddp.GradSync) and the record its overlap.
-    ``dump_dir``: rank 0 writes the last timed cycle's outputs there (dump_outputs) before anything else runs."""
+    ``dump_dir``: rank 0 writes the last timed cycle's outputs there (dump_outputs) before anything else runs.
+    ``full=False`` (a plain run's headline): the untimed cycles still run, so that the timed region starts from the same
+    state as with ``full``, but without the per-launch events, and the overlap cycles behind the timed region are left
+    out; the roofline is then the whole step's alone."""
     import torch
     module, trainer = build_trainer(expt, batch, device, world, force_sync, img_size, graph)
     data = synthetic_batch(batch, device, rank, img_size)
@@ -365,9 +377,11 @@ def measure(F, expt, batch, img_size, device, rank, world, steps, warmup, reps, 
     want_overlap = sync is not None and sync.measure
     if want_overlap:
         sync.measure = False
+    want_overlap = want_overlap and full
 
     def sample_kernels():
-        F.set_kernel_timer(timer)
+        if full:                                # a plain run: the same cycles, without the events
+            F.set_kernel_timer(timer)
         for _ in range((steps + TIMER_EVERY - 1) // TIMER_EVERY * len(trainer.order)):
             trainer.step(data)
         trainer.finish()
@@ -541,7 +555,7 @@ def gradsync_w1_records(F, args, device, use_timer, out, head_key):
 
 
 def compact_record(rec):
-    """A sub-configuration record reduced to its numbers (the default line; ``--detail`` prints the full records, and
+    """A sub-configuration record reduced to its numbers (a --full line; ``--detail`` prints the full records, and
     tools/profile_r06.sh commits that form as profiles/rNN_bench_line.json)."""
     out = {}
     if "workload" in rec:
@@ -608,10 +622,10 @@ def run_rank(args):
     if args.force_grad_sync and world == 1:       # the headline itself on the data-parallel code path (profiling runs)
         with single_rank_rccl(device):
             head = measure(F, args.expt, args.batch, args.img_size, device, rank, world, args.steps, args.warmup,
-                           args.reps, use_timer, True, args.graph, args.dump_outputs)
+                           args.reps, use_timer, True, args.graph, args.dump_outputs, args.full)
     else:
         head = measure(F, args.expt, args.batch, args.img_size, device, rank, world, args.steps, args.warmup, args.reps,
-                       use_timer, args.force_grad_sync, args.graph, args.dump_outputs)
+                       use_timer, args.force_grad_sync, args.graph, args.dump_outputs, args.full)
     head_key = config_key_of(args.expt, args.batch, args.img_size)
 
     out = {
@@ -644,8 +658,8 @@ def run_rank(args):
     if "dumped_outputs" in head:
         out["dumped_outputs"] = head["dumped_outputs"]
 
-    default_run = args.expt == "dc_gan" and args.img_size == 64 and not args.no_bs128
-    if default_run:
+    sub_run = args.full and args.expt == "dc_gan" and args.img_size == 64 and not args.no_bs128
+    if sub_run:
         # the other BASELINE configurations.  Every world size: dc_gan bs 512 / GPU (configs 2 and 4, the north star's
         # roofline batch), timed on ALL ranks exactly like the headline.  One GPU only: config 3 (wgan_gp bs 256),
         # config 5's per-GPU workload (hologan bs 64; 64x64 parity-pinned and EXT-128), wgan bs 512.
@@ -660,7 +674,7 @@ def run_rank(args):
             # The data-parallel CODE PATH on this one GPU: the same dc_gan trainer under
             # ddp.GradSync with a single-rank RCCL communicator -- flat gradient buffers, per-parameter hooks, bucketed
             # all-reduce calls on RCCL's stream, per-bucket optimizer steps at the layer gates, the deferred tail -- so
-            # that every driver run times it next to the plain trainer (``vs_plain`` = this / plain ms per pair).
+            # that every --full run times it next to the plain trainer (``vs_plain`` = this / plain ms per pair).
             try:
                 out["sub_configs"].update(gradsync_w1_records(F, args, device, use_timer, out, head_key))
             except Exception as e:  # noqa: BLE001 -- a broken RCCL install must not take the headline number with it
@@ -678,7 +692,7 @@ def run_rank(args):
                                           "(sub_configs.dc_gan_bs512)" % (big["value"], big["ms_per_step"],
                                                                           w.get("frac", float("nan"))))
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline and args.expt == "dc_gan":
+        if world == 1 and args.full and not args.no_cpu_baseline and args.expt == "dc_gan":
             out["cpu_baseline"] = cpu_baseline(128, 12.0)
             out["cpu_baseline"]["bs64"] = cpu_baseline(64, 7.0)        # BASELINE config 1's batch
         subs = out.pop("sub_configs", None)

@@ -82,7 +82,7 @@ def test_two_rank_bench_rehearsal_on_one_gpu():
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-                        "--reps", "1", "--no-cpu-baseline", "--no-kernel-timer"],
+                        "--reps", "1", "--full", "--no-cpu-baseline", "--no-kernel-timer"],
                        env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

@@ -14,7 +14,7 @@ for a in "--expt dc_gan --batch 128" "--expt dc_gan --batch 512" "--expt dc_gan 
       --no-cpu-baseline --no-sub-configs --no-kernel-timer > /dev/null 2>&1
 done
 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/reach/fid -- python3 bench.py --batch 128 --steps 1 --warmup 1 --reps 1 \
-    --no-cpu-baseline --no-gradsync-w1 --fid-samples 500 > /dev/null 2>&1
+    --full --no-cpu-baseline --no-gradsync-w1 --fid-samples 500 > /dev/null 2>&1
 python3 - <<PY > gpurun_out/${tag}_reached_kernels.txt
 import csv, glob, collections
 c = collections.Counter()

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Round-4 evidence, one gpurun call:  bash tools/profile_r04.sh <tag> [configs...]
 #   per bench configuration: rocprofv3 --kernel-trace --stats of the bench command
-#   -> profiles-ready files under gpurun_out/<tag>_*: kernel stats (csv) and the idle-gap digest (tools/gap_digest.py:
+#   -> profiles-ready files under $OUT_DIR/<tag>_*: kernel stats (csv) and the idle-gap digest (tools/gap_digest.py:
 #   idle time by preceding kernel + histogram), followed by the host's enqueue time per cycle measured WITHOUT the
 #   profiler (tools/host_profile.py --brief): the HIP API trace costs the host more per launch than the launch itself
 #   (r04a: 32 % idle under --hip-runtime-trace against 5-7 % without), so it cannot say whether the host was late.
@@ -10,7 +10,7 @@ cd /tmp && export TMPDIR=/tmp
 cd $GRAFT_REPO_ROOT
 tag=$1; shift
 cfgs=${@:-"dc_gan_bs128 dc_gan_bs512 wgan_gp_bs256 hologan_bs64 hologan_ext128_bs64"}
-mkdir -p gpurun_out
+out=${OUT_DIR:-bench_out}; mkdir -p $out      # where this script's files go
 for c in $cfgs; do
   case $c in
     dc_gan_bs128) a="--expt dc_gan --batch 128"; cyc=2;;
@@ -25,13 +25,13 @@ for c in $cfgs; do
   case $c in dc_gan*|wgan*) e=${c%%_bs*};; *) e=hologan;; esac
   timeout 400 rocprofv3 --kernel-trace ${HIPTRACE:+--hip-runtime-trace} --stats --output-format csv -d /tmp/prof_$c -- \
       python3 bench.py $a --steps 10 --warmup 2 --reps 1 --no-cpu-baseline --no-sub-configs --no-kernel-timer \
-      > gpurun_out/${tag}_${c}_prof_line.json 2> gpurun_out/${tag}_${c}_prof.err
+      > $out/${tag}_${c}_prof_line.json 2> $out/${tag}_${c}_prof.err
   ks=$(find /tmp/prof_$c -name "*kernel_stats.csv" | head -1)
   kt=$(find /tmp/prof_$c -name "*kernel_trace.csv" | head -1)
   ha=$(find /tmp/prof_$c -name "*hip_api_trace.csv" | head -1)
-  [ -n "$ks" ] && cp $ks gpurun_out/${tag}_${c}_kernel_stats.csv
-  [ -n "$kt" ] && python3 tools/gap_digest.py $kt "$ha" $cyc > gpurun_out/${tag}_gaps_${c}.txt 2>&1
+  [ -n "$ks" ] && cp $ks $out/${tag}_${c}_kernel_stats.csv
+  [ -n "$kt" ] && python3 tools/gap_digest.py $kt "$ha" $cyc > $out/${tag}_gaps_${c}.txt 2>&1
   python3 tools/host_profile.py $(echo $a | sed -e 's/--expt //' -e 's/--batch //' -e 's/--img-size //') --brief \
-      >> gpurun_out/${tag}_gaps_${c}.txt 2>/dev/null
+      >> $out/${tag}_gaps_${c}.txt 2>/dev/null
 done
-ls -la gpurun_out | tail -30
+ls -la $out | tail -30
