@@ -218,6 +218,19 @@ size_t gz_rigid_resample_bwd_workspace_bytes(int N, int S);
 int gz_rigid_resample_bwd(const float* gout2d, const float* minv, float* gvox, float* workspace, size_t ws_bytes,
                           int N, int C, int S, hipStream_t stream);
 
+/* gz_rigid_resample_fwd under V views of each of B sources (figures' view sweeps, forward only): vox [B,C,S,S,S],
+ * minv [B*V,16] (row b*V+v), out2d [B*V, C*S, S, S] in gz_rigid_resample_fwd's layout, bit-equal to it applied to
+ * the sources repeated V times; each source is read from HBM once per view chunk instead of once per view.
+ * Needs S^3 % 4 == 0, a 16-byte aligned vox and 4*S^3 floats of LDS (S <= 16). */
+int gz_rigid_resample_views_fwd(const float* vox, const float* minv, float* out2d, int B, int V, int C, int S,
+                                hipStream_t stream);
+
+/* ---- figures (core/figures/types.py): F frames of n images img [F*n, C, H, W] (C = 1 or 3) laid out as
+ * torchvision's make_grid (ncol per row, padding / pad_value, one image unpadded), clamped to [0, 1], x * 255.0f in
+ * fp32 truncated: out uint8 [F, GH, GW, 3] (4-byte aligned); GH x GW = make_grid's size for n images. */
+int gz_figure_frames_u8(const float* img, unsigned char* out, int F, int n, int C, int H, int W, int ncol, int padding,
+                        float pad_value, hipStream_t stream);
+
 /* ---- evaluation path: InceptionV3 feature extractor of FID / KID (core/callback_inception_metrics.py:183-246,
  * core/submodules/gan_stability/metrics/inception.py) -- forward only --------------------------------------------
  * y = act(conv2d(x, w) + bias) for ANY rectangular kernel, per-axis stride and padding (3x3 s2 p0, 5x5 s1 p2,

@@ -111,6 +111,10 @@ def _std_nets(cfg, root, **disc_extra):
         "features_g": t["features_gen"], "img_size": t["img_size"]}
 
 
+FIGURES_2D = (("sample_grid", "SampleGrid"), ("interpolation", "Interpolation"))
+FIGURES_3D = (("sample_grid", "SampleGrid"), ("interpolation3d", "Interpolation3d"), ("azimuth_step", "AzimuthStep"),
+              ("elevation_step", "ElevationStep"), ("azimuth_gif", "AzimuthGif"), ("elevation_gif", "ElevationGif"))
+
 PRIMARY = ("train", "model", "optimisation")      # nodes other nodes are derived from (the yaml's ${...} sources)
 
 
@@ -228,6 +232,12 @@ def make_cfg(expt, module_root=PRODUCT_ROOT, batch_size=None, features=None, img
         o["lr_scheduler"]["total_epochs"] = t["num_epochs"]
     cfg["disc_optimiser"] = copy.deepcopy(cfg["optimiser"])   # config.yaml:30-31
     cfg["gen_optimiser"] = copy.deepcopy(cfg["optimiser"])
+    # the figures of the experiment's defaults list, in its order (conf/expt/*.yaml), and conf/config.yaml:44-52
+    names = FIGURES_3D if expt == "hologan" else FIGURES_2D
+    cfg["figures"] = {key: {"_target_": module_root + ".figures.types." + cls} for key, cls in names}
+    cfg["figure_details"] = {"dir": "figures", "filename": "", "fid_callback": True, "save_all": False,
+                             "img_size": t["img_size"], "data_mean": t["data_mean"], "data_std": t["data_std"],
+                             "channels_img": t["channels_img"]}
     for k, v in dotted.items():
         if k.split(".")[0] not in PRIMARY:
             _assign(cfg, k, v)

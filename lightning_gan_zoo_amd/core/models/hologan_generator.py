@@ -215,6 +215,58 @@ class Generator(nn.Module):
                           "generator.prefetch_view = lambda n: None to draw views inside forward() only).", stacklevel=3)
         return None
 
+    def drop_prefetched_view(self):
+        """Undo the provisional draw of prefetch_view (numpy's global generator back to its state before it), so that
+        something else may draw from numpy before the next forward -- the figures at an epoch end -- and that forward
+        then draws its view where the reference does.  No-op without a pending prefetch."""
+        self._take_prefetched(-1)
+
+    @torch.no_grad()
+    def render_views(self, z, views, max_rows=256):
+        """Images of every object under every view, inference only: z [B, Z]; views [V, 6] (the same views for all
+        objects) or [B, V, 6], tensor or numpy, converted to matrices exactly as forward(z, view_in=...) converts them
+        (no numpy draw).  -> [B, V, C, H, W], ``[b, v] == forward(z[b:b+1], view_in=views[v:v+1])[0]`` up to the
+        rounding of batch-size dependent kernel choices.  The z-dependent trunk (the five ZMapping layers, the AdaIN'd
+        constant, block1, block2) runs once per object; the B*V resampled volumes come out of one multi-view gather
+        per chunk, and the 2-D tail runs over chunks of at most ``max_rows`` (object, view) rows, whole objects each."""
+        B, dev = z.shape[0], self.x.device
+        v = torch.from_numpy(views) if isinstance(views, np.ndarray) else torch.as_tensor(views)
+        v = v.cpu()
+        if v.dim() == 2:
+            V = v.shape[0]
+            minv_v = view_inverse_matrices(v).reshape(V, 16)
+            minv = draw_on_host(lambda: minv_v.repeat(B, 1).contiguous(), dev)
+        elif v.dim() == 3 and v.shape[0] == B:
+            V = v.shape[1]
+            minv = draw_on_host(lambda: view_inverse_matrices(v.reshape(B * V, v.shape[2])).reshape(B * V, 16)
+                                .contiguous(), dev)
+        else:
+            raise ValueError("views must be [V, 6] or [%d, V, 6], got %s" % (B, tuple(v.shape)))
+        maps = self._zmaps()
+        F.ready(*[p for m in maps for p in (m.linear1.weight, m.linear1.bias)])
+        s0, s1, s2, s3, s4 = F.linear_act_multi(z, [(m.linear1.weight, m.linear1.bias) for m in maps], F.ACT_RELU)
+        F.ready(self.x)
+        h = F.adain_const_act(self.x, s0, 1e-8, F.ACT_RELU)
+        h = self.block1(h, z, s1)
+        vox = self.block2(h, z, s2).contiguous()               # [B, C, 16, 16, 16]
+        p, f = self.convTranspose2d1, self.final_layer
+        F.ready(p.weight, p.bias, f.weight, f.bias)
+        per = max(1, max_rows // V)                             # whole objects per chunk
+        out = []
+        for b0 in range(0, B, per):
+            b1 = min(B, b0 + per)
+            h = F.rigid_resample_views(vox[b0:b1], minv[b0 * V:b1 * V])     # [(b1-b0)*V, 16*C, 16, 16]
+            h = F.conv_transpose2d(h, p.weight, p.bias, K1S1P0, F.ACT_RELU)
+            h = self.block3(h, None, s3[b0:b1].repeat_interleave(V, 0))
+            h = self.block4(h, None, s4[b0:b1].repeat_interleave(V, 0))
+            if isinstance(f, nn.ConvTranspose2d):                           # EXT-128
+                h = F.conv_transpose2d(h, f.weight, f.bias, F.K4S2P1, F.ACT_TANH)
+            else:
+                h = F.conv2d(h, f.weight, f.bias, K3S1P1, F.ACT_TANH)
+            out.append(h)
+        imgs = out[0] if len(out) == 1 else torch.cat(out)
+        return imgs.reshape(B, V, *imgs.shape[1:])
+
     def forward(self, z, view_in=None):
         n = z.shape[0]
         dev = self.x.device

@@ -5,6 +5,7 @@
 // result is written directly in the layout the "learned projection" consumes:
 //     out2d[n][c*S + (S-1-y)][z][x]      (= permute(0,1,3,2,4) -> flip(dim 2) -> reshape, :130-133)
 // HBM-bound gather (forward) / float-atomic scatter-add (backward; 8 adds of 4 B per output element).
+#include <algorithm>
 #include <cstdlib>
 #include "gz_common.h"
 #include "gz_knobs.h"
@@ -135,6 +136,49 @@ __global__ __launch_bounds__(RS_THREADS) void resample_fwd_staged_kernel(const f
 #pragma unroll
         for (int j = 0; j < FW_LC; ++j)
             if (j < lc) out[(((long long)n * C * S + (long long)(c0 + j) * S + (S - 1 - y)) * S + z) * S + x] = acc[j];
+    }
+}
+
+// Forward under V views of each source (figures: one object rendered along a sweep of views).  The staged kernel
+// above reads a source's FW_LC channel volumes from HBM once per OUTPUT sample, so V views of B objects through it read
+// every source V times.  Here a workgroup stages the volumes of source b once, with the same placement, and emits them
+// under the views [v0, v1) of its chunk: output row n = b * V + v, matrix minv[n].  Same corners(), same LDS reads, same
+// accumulation expression: the result is bit-equal to resample_fwd_staged_kernel over the source repeated V times.
+__global__ __launch_bounds__(RS_THREADS) void resample_fwd_views_kernel(const float* __restrict__ vox,
+                                                                        const float* __restrict__ minv,
+                                                                        float* __restrict__ out, int V, int C, int S,
+                                                                        int sh, int vchunk) {
+    static_assert(FW_LC == 4, "one f32x4 per corner");
+    extern __shared__ __attribute__((aligned(16))) float vl[];
+    const int S3 = S * S * S;
+    const int b = blockIdx.x;
+    const int c0 = blockIdx.y * FW_LC;
+    const int lc = min(FW_LC, C - c0);
+    const int v0 = blockIdx.z * vchunk, v1 = min(V, v0 + vchunk);
+    const float* src = vox + ((long long)b * C + c0) * S3;
+    for (int i = threadIdx.x * 4; i < FW_LC * S3; i += RS_THREADS * 4) {
+        const int j = i / S3, u = i - j * S3;
+        const f32x4 v = j < lc ? *reinterpret_cast<const f32x4*>(src + i) : f32x4{0.f, 0.f, 0.f, 0.f};
+        vl[lds_slot(u + 0, sh) * FW_LC + j] = v[0];
+        vl[lds_slot(u + 1, sh) * FW_LC + j] = v[1];
+        vl[lds_slot(u + 2, sh) * FW_LC + j] = v[2];
+        vl[lds_slot(u + 3, sh) * FW_LC + j] = v[3];
+    }
+    __syncthreads();
+    const f32x4* vq = reinterpret_cast<const f32x4*>(vl);
+    for (int vi = v0; vi < v1; ++vi) {
+        const long long n = (long long)b * V + vi;
+        const float* m = minv + n * 16;
+        for (int r = threadIdx.x; r < S3; r += RS_THREADS) {
+            const int z = r / (S * S), y = (r / S) % S, x = r % S;
+            Corner8 cn = corners(m, x, y, z, S);
+            f32x4 acc = vq[lds_slot(cn.off[0], sh)] * cn.w[0];
+#pragma unroll
+            for (int k = 1; k < 8; ++k) acc = acc + vq[lds_slot(cn.off[k], sh)] * cn.w[k];   // as the staged kernel
+#pragma unroll
+            for (int j = 0; j < FW_LC; ++j)
+                if (j < lc) out[((n * C * S + (long long)(c0 + j) * S + (S - 1 - y)) * S + z) * S + x] = acc[j];
+        }
     }
 }
 
@@ -439,6 +483,26 @@ int gz_rigid_resample_fwd(const float* vox, const float* minv, float* out2d, lon
     long long vox_n = (long long)N * S * S * S;
     dim3 grid((unsigned)((vox_n + RS_THREADS - 1) / RS_THREADS), (C + RS_CB - 1) / RS_CB);
     hipLaunchKernelGGL(resample_fwd_kernel, grid, dim3(RS_THREADS), 0, stream, vox, minv, out2d, idx_out, N, C, S);
+    return launch_status();
+}
+
+int gz_rigid_resample_views_fwd(const float* vox, const float* minv, float* out2d, int B, int V, int C, int S,
+                                hipStream_t stream) {
+    gz::clear_stale_error();
+    if (B <= 0 || V <= 0 || C <= 0 || S <= 0) return GZ_ERR_BAD_SHAPE;
+    const int S3 = S * S * S;
+    const size_t lds = (size_t)FW_LC * S3 * sizeof(float);
+    if (S3 % 4 || (((uintptr_t)vox) & 15)) return GZ_ERR_BAD_SHAPE;
+    if (lds > 64 * 1024) return GZ_ERR_UNSUPPORTED;
+    // Grid (sources, channel groups, view chunks).  64 KiB of LDS per workgroup at S = 16 leaves room for two per CU:
+    // the views are split into just enough chunks for ~2 x 256 workgroups (B = 4, C = 64: 8 chunks; B = 16: 2), each
+    // chunk staging its source again -- an extra 64 KiB read per chunk against V x 64 KiB written per group.
+    const long long groups = (long long)B * ((C + FW_LC - 1) / FW_LC);
+    const int want = (int)std::min<long long>(V, std::max<long long>(1, (512 + groups - 1) / groups));
+    const int vchunk = (V + want - 1) / want;
+    const int chunks = (V + vchunk - 1) / vchunk;
+    hipLaunchKernelGGL(resample_fwd_views_kernel, dim3(B, (C + FW_LC - 1) / FW_LC, chunks), dim3(RS_THREADS), lds,
+                       stream, vox, minv, out2d, V, C, S, swizzle_shift(S), vchunk);
     return launch_status();
 }
 

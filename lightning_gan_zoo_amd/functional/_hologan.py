@@ -384,6 +384,19 @@ def rigid_resample(vox, minv):
     return _RigidResample.apply(vox, minv)
 
 
+def rigid_resample_views(vox, minv):
+    """Forward only: [B,C,S,S,S] voxels under V views each, ``minv`` [B*V, 16] (row b*V + v) -> [B*V, C*S, S, S],
+    bit-equal to ``rigid_resample(vox.repeat_interleave(V, 0), minv)`` with each source read once per view chunk."""
+    vox, minv = _req(vox, "vox"), _req(minv, "minv")
+    B, C, S = vox.shape[0], vox.shape[1], vox.shape[2]
+    if minv.shape[0] % B or minv.numel() != minv.shape[0] * 16:
+        raise ValueError("minv must be [B*V, 16] for %d sources, got %s" % (B, tuple(minv.shape)))
+    V = minv.shape[0] // B
+    out = torch.empty((B * V, C * S, S, S), device=vox.device, dtype=torch.float32)
+    check(lib.gz_rigid_resample_views_fwd(_p(vox), _p(minv), _p(out), B, V, C, S, _stream()), "rigid_resample_views_fwd")
+    return out
+
+
 def rigid_resample_indices(vox, minv):
     """Debug / test hook: the int64 corner indices idx_a..idx_h the kernel uses, [8, N*S^3]."""
     N, C, S = vox.shape[0], vox.shape[1], vox.shape[2]

@@ -434,4 +434,32 @@ def normalize_u8_images(u8, mean, std):
     return out
 
 
+
+# ---------------------------------------------------------------------------
+# figures (core/figures/types.py)
+# ---------------------------------------------------------------------------
+def figure_frame_dims(n, H, W, ncol, padding=2):
+    """(GH, GW) of make_grid over ``n`` images of H x W, ``ncol`` per row; one image is returned unpadded."""
+    if n == 1:
+        return H, W
+    xmaps = min(ncol, n)
+    ymaps = -(-n // xmaps)
+    return (H + padding) * ymaps + padding, (W + padding) * xmaps + padding
+
+
+def figure_frames_u8(img, frames, ncol, padding=2, pad_value=0.0):
+    """``frames`` grids of ``img.shape[0] // frames`` consecutive images each ([F*n, C, H, W] floats, C = 1 or 3) ->
+    uint8 [F, GH, GW, 3] = ``(clamp(make_grid(cell images, nrow=ncol, padding, pad_value).permute(1, 2, 0), 0, 1)
+    * 255).astype(...)`` per frame: fp32 product truncated toward zero, one launch for all frames."""
+    img = _req(img, "img")
+    N, C, H, W = img.shape
+    if frames <= 0 or N % frames:
+        raise ValueError("%d images do not split into %d frames" % (N, frames))
+    n = N // frames
+    GH, GW = figure_frame_dims(n, H, W, ncol, padding)
+    out = torch.empty((frames, GH, GW, 3), device=img.device, dtype=torch.uint8)
+    check(lib.gz_figure_frames_u8(_p(img), _p(out), frames, n, C, H, W, ncol, padding, float(pad_value), _stream()),
+          "figure_frames_u8")
+    return out
+
 __all__ = [n for n in list(globals()) if not n.startswith("__")]     # the flat namespace of the package (private helpers included)

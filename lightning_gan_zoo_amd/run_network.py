@@ -35,7 +35,7 @@ from .config import ConfigError, compose_tree, locate, make_cfg, parse_value
 
 # keys of this runner, not of the reference's config (accepted with or without Hydra's "+")
 RUNNER_KEYS = {"max_steps": None, "log_every": 10, "dataset_path": None, "seed": 42, "steps_per_epoch": 100,
-               "inception_weights": None, "inception_check_hash": True}
+               "inception_weights": None, "inception_check_hash": True, "figures": False}
 BUILTIN_DATASETS = ("synthetic", "image_folder", "tensor_file", "celeb_a")
 LIGHTNING_VERSION_TAG = "1.2.0"       # envelope layout written below (Lightning 1.1 / 1.2 generation)
 
@@ -425,9 +425,10 @@ class CheckpointKeeper:
 # ---------------------------------------------------------------------------------------------------------
 # the loop
 # ---------------------------------------------------------------------------------------------------------
-def fit(module, cfg, data, run, sync=None, rank=0, world=1, evaluate=None, slow_group=None):
+def fit(module, cfg, data, run, sync=None, rank=0, world=1, evaluate=None, slow_group=None, figures=None):
     """``pl.Trainer(max_epochs=cfg.train.num_epochs, resume_from_checkpoint=find_ckpt(...)).fit(model)`` for the
-    step classes of this package (reference run_network.py:61-72).  Returns (module, trainer, global_step)."""
+    step classes of this package (reference run_network.py:61-72).  ``figures``: an EpochFigures, drawn at every epoch
+    end after the FID evaluation.  Returns (module, trainer, global_step)."""
     from .harness import Trainer
     t = cfg.train
     # reference run_network.py:61-68: ``1`` or a ``{start_epoch, accumulation_factor}`` node -> Lightning's
@@ -498,11 +499,61 @@ def fit(module, cfg, data, run, sync=None, rank=0, world=1, evaluate=None, slow_
             metrics = evaluate(module, epoch) if evaluate is not None else None
             if slow_group is not None:    # ranks > 0 wait for rank 0's Inception pass on the long-timeout group
                 torch.distributed.barrier(group=slow_group)
+            if figures is not None:
+                figures(module, epoch - 1, metrics, sync)
             checkpoint(metrics)
     trainer.finish()
     if step % steps_per_epoch:            # a run cut short by max_steps still leaves a resumable state
         checkpoint(None)
     return module, trainer, step
+
+
+class EpochFigures:
+    """The reference's figure callbacks at a validation end (core/figures/types.py:78-91, run on_validation_end after
+    InceptionMetrics' on_validation_epoch_start has logged this epoch's FID): each figure whose monitor rule passes
+    draws and writes.  Pending gradient exchanges and optimizer steps land first; the module runs in eval mode under
+    no_grad and gets its mode back.  HoloGAN's view prefetched for the next step is rolled back first, so that numpy's
+    stream reads (figure draws, next step's view) as in the reference.  Every rank makes the same host draws (the
+    reference draws on every rank and saves on rank zero); only rank 0 renders and writes.  ``have_fid``: an FID
+    evaluator exists (on rank 0); without one a monitored figure is drawn every epoch, and says so once."""
+
+    def __init__(self, figs, have_fid, rank=0, world=1, group=None):
+        self.figs, self.have_fid, self.rank, self.world, self.group = list(figs), have_fid, rank, world, group
+        self._said = False
+
+    def score(self, metrics):
+        fid = None if not metrics or metrics.get("fid") is None else float(metrics["fid"])
+        if self.world > 1 and self.have_fid:
+            t = torch.tensor([float("nan") if fid is None else fid], dtype=torch.float64)
+            torch.distributed.broadcast(t, 0, group=self.group)
+            fid = None if math.isnan(float(t[0])) else float(t[0])
+        return fid
+
+    def __call__(self, module, epoch, metrics, sync=None):
+        score = self.score(metrics)
+        if not self.have_fid and not self._said and any(f.monitor for f in self.figs):
+            self._said = True
+            if self.rank == 0:
+                print("figures: figure_details.fid_callback is set but no FID is computed in this run (no "
+                      "inception_weights / ImageFolder validation set): the monitor is off, figures are drawn every "
+                      "epoch")
+        if sync is not None:
+            sync.flush()
+        gen = module.generator
+        if hasattr(gen, "drop_prefetched_view"):
+            gen.drop_prefetched_view()
+        was = module.training
+        module.eval()
+        try:
+            with torch.no_grad():
+                for fig in self.figs:
+                    if not fig.should_draw(score if self.have_fid else None):
+                        continue
+                    plan = fig.plan(module)              # host draws: every rank
+                    if self.rank == 0:
+                        fig.write(fig.render(module, plan)[1].cpu().numpy(), epoch)
+        finally:
+            module.train(was)
 
 
 FID_IMAGE_EXTENSIONS = ("bmp", "jpg", "jpeg", "pgm", "png", "ppm", "tif", "tiff", "webp")
@@ -648,8 +699,18 @@ def main(argv=None):
                 print("FID evaluator could not be built on rank 0: %r" % (failure,), file=sys.stderr)
             torch.distributed.destroy_process_group()
             raise SystemExit(2)
+    figures = None
+    if run["figures"]:
+        from .core.figures.types import build_figures
+        try:
+            figs = build_figures(cfg, module, module.logging_dir)
+        except ValueError as e:
+            raise SystemExit("figures: %s" % e) from e
+        figures = EpochFigures(figs, have_fid=evaluate is not None or slow_group is not None, rank=rank, world=world,
+                               group=slow_group)
     data = build_data(cfg, run, device, rank, world)
-    out = fit(module, cfg, data, run, sync=sync, rank=rank, world=world, evaluate=evaluate, slow_group=slow_group)
+    out = fit(module, cfg, data, run, sync=sync, rank=rank, world=world, evaluate=evaluate, slow_group=slow_group,
+              figures=figures)
     if world > 1:
         torch.distributed.destroy_process_group()
     return out
