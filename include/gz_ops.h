@@ -473,6 +473,15 @@ int gz_upsample2_bwd(const float* gy, float* gx, long long planes, int H, int W,
  * core/lightning_module.py:42-47 on the device */
 int gz_u8hwc_to_nchw(const unsigned char* in, float* out, int N, int H, int W, int C, float mean, float std,
                      hipStream_t stream);
+/* the same step for a batch drawn from a uint8 set [M,H,W,C] that stays on the device:
+ *   out[i,c,h,w] = (set[idx[i],h,w,c] / 255 - mean) / std,  labels_out[i] = labels[idx[i]]
+ * for i < n, bit-equal to gz_u8hwc_to_nchw over the rows set[idx].  idx (int64 [n]) and labels (int64 [M], or NULL
+ * together with labels_out) are device pointers; row byte offsets are 64-bit, so M*H*W*C is unbounded while n*H*W
+ * < 2^31 (GZ_ERR_TOO_LARGE).  An idx[i] outside [0, M) is not dereferenced: row i of out is written as quiet NaN and
+ * labels_out[i] as -1. */
+int gz_u8hwc_gather_to_nchw(const unsigned char* set, long long M, const long long* idx, const long long* labels,
+                            float* out, long long* labels_out, int n, int H, int W, int C, float mean, float std,
+                            hipStream_t stream);
 
 /* ---- fused multi-tensor optimizer steps (the `optimiser` nodes of conf/expt/<name>.yaml) -------------------------
  * `count` <= GZ_OPT_MAX_TENSORS tensors per call (host arrays of device pointers and element counts);

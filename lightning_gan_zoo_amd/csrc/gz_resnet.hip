@@ -202,6 +202,11 @@ int gz_upsample2_bwd(const float* gy, float* gx, long long planes, int H, int W,
 // written per element) instead of on the host.  One thread per output pixel, all channels.
 // ---------------------------------------------------------------------------
 namespace gz {
+// the one expression of the input step: (x / 255 - mean) / std as x * scale + shift.  Both kernels below call it, so
+// the compiler contracts (or does not contract) the multiply-add the same way in both and their results agree bit
+// for bit.
+__device__ __forceinline__ float u8_norm(unsigned char v, float scale, float shift) { return (float)v * scale + shift; }
+
 __global__ __launch_bounds__(256) void u8hwc_to_nchw_kernel(const unsigned char* __restrict__ in,
                                                             float* __restrict__ out, long long pixels, int HW, int C,
                                                             float scale, float shift, FastDiv div_hw) {
@@ -211,8 +216,72 @@ __global__ __launch_bounds__(256) void u8hwc_to_nchw_kernel(const unsigned char*
         const uint32_t pix = (uint32_t)p - n * (uint32_t)HW;
         const unsigned char* src = in + p * C;
         float* dst = out + (long long)n * C * HW + pix;
-        for (int c = 0; c < C; ++c) dst[(long long)c * HW] = (float)src[c] * scale + shift;
+        for (int c = 0; c < C; ++c) dst[(long long)c * HW] = u8_norm(src[c], scale, shift);
     }
+}
+
+// Resident training set: batch row i is row idx[i] of a uint8 [M, H, W, C] set that stays in HBM.  One thread takes
+// PX consecutive pixels of one batch row with all their channels.  WIDE (PX = 4) needs H*W % 4 == 0 and aligned base
+// pointers: then every row, and every group of 4 pixels in it, starts on a 4-byte boundary of the set and on a
+// 16-byte boundary of each output plane, so a lane reads C dwords (lanes back to back: 4*C bytes each) and writes one
+// float4 per plane (lanes back to back: 16 bytes each).  Otherwise (PX = 1; e.g. rows of 5*7*3 = 105 bytes) the
+// accesses are byte loads and dword stores, the mapping of u8hwc_to_nchw_kernel.  The row's byte offset idx[i]*H*W*C
+// is 64-bit.  An index outside [0, M) is never used as an address: its row is written as quiet NaN, its label as -1.
+template <int C, bool WIDE>
+__global__ __launch_bounds__(256) void u8hwc_gather_kernel(const unsigned char* __restrict__ set, long long M,
+                                                           const long long* __restrict__ idx,
+                                                           const long long* __restrict__ labels,
+                                                           float* __restrict__ out, long long* __restrict__ labels_out,
+                                                           long long items, int HW, int G, float scale, float shift,
+                                                           FastDiv div_g) {
+    constexpr int PX = WIDE ? 4 : 1;
+    const long long stride = (long long)gridDim.x * 256;
+    for (long long p = (long long)blockIdx.x * 256 + threadIdx.x; p < items; p += stride) {
+        const uint32_t i = fdiv((uint32_t)p, div_g);
+        const uint32_t g = (uint32_t)p - i * (uint32_t)G;
+        const long long row = idx[i];
+        const bool ok = row >= 0 && row < M;
+        if (g == 0 && labels_out != nullptr) labels_out[i] = ok ? labels[row] : -1ll;
+        float* dst = out + (long long)i * C * HW + (long long)g * PX;
+        float v[C][PX];
+        if (!ok) {
+            for (int c = 0; c < C; ++c)
+                for (int k = 0; k < PX; ++k) v[c][k] = __builtin_nanf("");
+        } else {
+            const unsigned char* src = set + row * ((long long)HW * C) + (long long)g * (PX * C);
+            if constexpr (WIDE) {
+                uint32_t w[C];
+                for (int j = 0; j < C; ++j) w[j] = reinterpret_cast<const uint32_t*>(src)[j];
+                for (int k = 0; k < PX; ++k)
+                    for (int c = 0; c < C; ++c) {
+                        const int b = k * C + c;
+                        v[c][k] = u8_norm((unsigned char)((w[b >> 2] >> (8 * (b & 3))) & 0xffu), scale, shift);
+                    }
+            } else {
+                for (int c = 0; c < C; ++c) v[c][0] = u8_norm(src[c], scale, shift);
+            }
+        }
+        for (int c = 0; c < C; ++c) {
+            if constexpr (WIDE) {
+                f32x4 q = {v[c][0], v[c][1], v[c][2], v[c][3]};
+                *reinterpret_cast<f32x4*>(dst + (long long)c * HW) = q;
+            } else {
+                dst[(long long)c * HW] = v[c][0];
+            }
+        }
+    }
+}
+
+template <int C>
+static void launch_u8hwc_gather(bool wide, int grid, hipStream_t stream, const unsigned char* set, long long M,
+                                const long long* idx, const long long* labels, float* out, long long* labels_out,
+                                long long items, int HW, int G, float scale, float shift) {
+    if (wide)
+        hipLaunchKernelGGL((u8hwc_gather_kernel<C, true>), dim3(grid), dim3(256), 0, stream, set, M, idx, labels, out,
+                           labels_out, items, HW, G, scale, shift, make_fastdiv(G));
+    else
+        hipLaunchKernelGGL((u8hwc_gather_kernel<C, false>), dim3(grid), dim3(256), 0, stream, set, M, idx, labels, out,
+                           labels_out, items, HW, G, scale, shift, make_fastdiv(G));
 }
 }  // namespace gz
 
@@ -225,5 +294,29 @@ extern "C" int gz_u8hwc_to_nchw(const unsigned char* in, float* out, int N, int 
     // (x / 255 - mean) / std  =  x * (1 / (255 std)) - mean / std
     hipLaunchKernelGGL(gz::u8hwc_to_nchw_kernel, dim3(gz::rn_grid(pixels)), dim3(256), 0, stream, in, out, pixels, H * W,
                        C, 1.f / (255.f * std), -mean / std, gz::make_fastdiv(H * W));
+    return gz::launch_status();
+}
+
+extern "C" int gz_u8hwc_gather_to_nchw(const unsigned char* set, long long M, const long long* idx,
+                                       const long long* labels, float* out, long long* labels_out, int n, int H, int W,
+                                       int C, float mean, float std, hipStream_t stream) {
+    gz::clear_stale_error();
+    if (M <= 0 || n <= 0 || H <= 0 || W <= 0 || C <= 0 || C > 4 || std == 0.f) return GZ_ERR_BAD_SHAPE;
+    if (set == nullptr || idx == nullptr || out == nullptr) return GZ_ERR_BAD_SHAPE;
+    const long long pixels = (long long)n * H * W;
+    if (pixels >= (1ll << 31)) return GZ_ERR_TOO_LARGE;
+    const int HW = H * W;
+    const bool wide = HW % 4 == 0 && (uintptr_t)set % 4 == 0 && (uintptr_t)out % 16 == 0;
+    const int G = wide ? HW / 4 : HW;
+    const long long items = (long long)n * G;
+    if (labels == nullptr) labels_out = nullptr;
+    const float scale = 1.f / (255.f * std), shift = -mean / std;      // as gz_u8hwc_to_nchw
+    const int grid = gz::rn_grid(items);
+    switch (C) {
+        case 1: gz::launch_u8hwc_gather<1>(wide, grid, stream, set, M, idx, labels, out, labels_out, items, HW, G, scale, shift); break;
+        case 2: gz::launch_u8hwc_gather<2>(wide, grid, stream, set, M, idx, labels, out, labels_out, items, HW, G, scale, shift); break;
+        case 3: gz::launch_u8hwc_gather<3>(wide, grid, stream, set, M, idx, labels, out, labels_out, items, HW, G, scale, shift); break;
+        default: gz::launch_u8hwc_gather<4>(wide, grid, stream, set, M, idx, labels, out, labels_out, items, HW, G, scale, shift); break;
+    }
     return gz::launch_status();
 }

@@ -434,6 +434,33 @@ def normalize_u8_images(u8, mean, std):
     return out
 
 
+def gather_normalize_u8(set_u8, idx, mean, std, labels=None):
+    """A batch from a uint8 set [M,H,W,C] resident on the GPU: rows ``idx`` (int64, on the same device) ->
+    (float [n,C,H,W] = (set[idx] / 255 - mean) / std, ``labels[idx]`` or None), one launch on the current stream, bit-equal
+    to ``normalize_u8_images(set_u8[idx])``.  An index outside [0, M) is not read: its image is NaN, its label -1.
+    No autograd."""
+    if not set_u8.is_cuda or set_u8.dtype != torch.uint8 or set_u8.dim() != 4:
+        raise RuntimeError("lightning_gan_zoo_amd: expected a uint8 NHWC tensor on the GPU")
+    if not set_u8.is_contiguous():
+        raise RuntimeError("lightning_gan_zoo_amd: the resident uint8 set must be contiguous")
+    if idx.dtype != torch.int64 or idx.dim() != 1 or idx.device != set_u8.device:
+        raise RuntimeError("lightning_gan_zoo_amd: expected a 1-D int64 index tensor on the set's device")
+    idx = idx if idx.is_contiguous() else idx.contiguous()
+    M, H, W, C = set_u8.shape
+    n = idx.numel()
+    lab_out = None
+    if labels is not None:
+        if labels.dtype != torch.int64 or labels.shape != (M,) or labels.device != set_u8.device \
+                or not labels.is_contiguous():
+            raise RuntimeError("lightning_gan_zoo_amd: expected contiguous int64 labels [M] on the set's device")
+        lab_out = torch.empty((n,), device=set_u8.device, dtype=torch.int64)
+    out = torch.empty((n, C, H, W), device=set_u8.device, dtype=torch.float32)
+    check(lib.gz_u8hwc_gather_to_nchw(_p(set_u8), M, _p(idx), None if labels is None else _p(labels), _p(out),
+                                      None if lab_out is None else _p(lab_out), n, H, W, C, float(mean), float(std),
+                                      _stream()), "u8hwc_gather_to_nchw")
+    return out, lab_out
+
+
 
 # ---------------------------------------------------------------------------
 # figures (core/figures/types.py)

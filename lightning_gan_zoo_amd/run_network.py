@@ -35,8 +35,11 @@ from .config import ConfigError, compose_tree, locate, make_cfg, parse_value
 
 # keys of this runner, not of the reference's config (accepted with or without Hydra's "+")
 RUNNER_KEYS = {"max_steps": None, "log_every": 10, "dataset_path": None, "seed": 42, "steps_per_epoch": 100,
-               "inception_weights": None, "inception_check_hash": True, "figures": False}
-BUILTIN_DATASETS = ("synthetic", "image_folder", "tensor_file", "celeb_a")
+               "inception_weights": None, "inception_check_hash": True, "figures": False,
+               # resident training set (resident_data.py): decode once, keep the uint8 set in HBM, one gather launch per
+               # batch; data_cache = directory of the decoded-set cache file; a set above resident_max_gb is refused
+               "resident_data": False, "data_cache": None, "resident_max_gb": 32}
+BUILTIN_DATASETS = ("synthetic", "image_folder", "tensor_file", "celeb_a", "mnist")
 LIGHTNING_VERSION_TAG = "1.2.0"       # envelope layout written below (Lightning 1.1 / 1.2 generation)
 
 
@@ -84,6 +87,13 @@ def _builtin_dataset(name, run, filepaths):
             raise SystemExit("dataset=celeb_a needs filepaths.celeb_a_root=<dir> (conf/filepaths/example.yaml)")
         return {"_target_": "torchvision.datasets.ImageFolder", "n_channels": 3, "root": root,
                 "train": {"root": root + "/train"}, "val": {"root": root + "/train"}, "test": {"root": root + "/train"}}
+    if name == "mnist":                   # conf/dataset/mnist.yaml:1-20 (download is carried along, never acted on)
+        parent = filepaths.get("mnist_parent_directory") or run["dataset_path"]     # checked where it is opened
+        node = {"_target_": "torchvision.datasets.MNIST", "n_channels": 1, "parent_directory": parent,
+                "root": parent + "/MNIST" if parent else None, "download": True}
+        for split, train in (("train", True), ("val", False), ("test", False)):
+            node[split] = {"root": parent, "_target_": node["_target_"], "download": True, "train": train}
+        return node
     raise SystemExit("unknown dataset %r (built in: %s)" % (name, ", ".join(BUILTIN_DATASETS)))
 
 
@@ -311,8 +321,9 @@ class ImageFolderImages:
                    torch.from_numpy(labels).to(self.device, non_blocking=True))
 
 
-def build_data(cfg, run, device, rank=0, world=1):
-    """The training set of ``cfg.dataset`` (reference ``instantiate(cfg.dataset.train, transform=...)``, :89-92)."""
+def build_data(cfg, run, device, rank=0, world=1, group=None):
+    """The training set of ``cfg.dataset`` (reference ``instantiate(cfg.dataset.train, transform=...)``, :89-92).
+    ``group``: the long-timeout process group the ranks of a resident set wait on while rank 0 decodes."""
     t = cfg.train
     node = cfg.get("dataset") or {}
     target = str(node.get("_target_", ""))
@@ -321,11 +332,27 @@ def build_data(cfg, run, device, rank=0, world=1):
     train = node.get("train", node)
     if target.endswith("TensorFileImages"):
         return TensorFileImages(train["root"], t.batch_size, device, rank, world)
+    resident = dict(cache_dir=run.get("data_cache"), max_gb=run.get("resident_max_gb", 32), rank=rank, world=world,
+                    group=group)
+    if target.endswith("datasets.MNIST"):
+        if not run.get("resident_data"):
+            raise SystemExit("dataset target %r is served by the resident training set only: pass resident_data=true "
+                             "(60 000 x 64x64 bytes = 246 MB of HBM)" % target)
+        if not train.get("root"):
+            raise SystemExit("dataset=mnist needs filepaths.mnist_parent_directory=<dir holding MNIST/raw> "
+                             "(conf/filepaths/example.yaml) or dataset_path=<that dir>")
+        from .resident_data import ResidentImages
+        return ResidentImages(train["root"], t.batch_size, t.img_size, t.channels_img, t.data_mean, t.data_std, device,
+                              source="mnist", train=bool(train.get("train", True)), **resident)
+    if target.endswith("ImageFolder") and run.get("resident_data"):
+        from .resident_data import ResidentImages
+        return ResidentImages(train["root"], t.batch_size, t.img_size, t.channels_img, t.data_mean, t.data_std, device,
+                              source="image_folder", **resident)
     if target.endswith("ImageFolder"):
         return ImageFolderImages(train["root"], t.batch_size, t.img_size, t.channels_img, t.data_mean, t.data_std,
                                  device, rank=rank, world=world)
-    raise SystemExit("dataset target %r is not supported by this runner (ImageFolder-shaped datasets, tensor files "
-                     "and synthetic batches are)" % target)
+    raise SystemExit("dataset target %r is not supported by this runner (ImageFolder-shaped datasets, MNIST raw files, "
+                     "tensor files and synthetic batches are)" % target)
 
 
 # ---------------------------------------------------------------------------------------------------------
@@ -708,7 +735,13 @@ def main(argv=None):
             raise SystemExit("figures: %s" % e) from e
         figures = EpochFigures(figs, have_fid=evaluate is not None or slow_group is not None, rank=rank, world=world,
                                group=slow_group)
-    data = build_data(cfg, run, device, rank, world)
+    data_group = slow_group
+    if world > 1 and run["resident_data"] and data_group is None:
+        # rank 0 decodes the whole training set once while the others wait for its cache file: the same kind of
+        # start-up wait as the FID statistics above, on a group of the same kind
+        import datetime
+        data_group = torch.distributed.new_group(timeout=datetime.timedelta(hours=6), backend="gloo")
+    data = build_data(cfg, run, device, rank, world, group=data_group)
     out = fit(module, cfg, data, run, sync=sync, rank=rank, world=world, evaluate=evaluate, slow_group=slow_group,
               figures=figures)
     if world > 1:
