@@ -37,6 +37,51 @@ enum TileId { T128x128 = 0, T128x64 = 1, T128x32 = 2, T64x64 = 3, T256x256 = 4, 
               T256x128P = 9 };   // (a label only: ConvDg5A2's 256 pixels x (2 column phases x 64 channels), gz_conv2d_tile)
 static bool is_tile2(TileId t) { return t >= T256x256; }
 
+// ---- one launch choice per conv2d op ---------------------------------------------------------------------------------
+// choose_fwd / choose_dgrad / choose_wgrad (below, after the run_* functions they pick from) answer "which kernel does
+// this launch take" once: launch_* switch on the answer, the stats entry points check it, gz_conv2d_plan prints it.
+enum Kind { KUnsupported, KDirect, KIgemm, KIgemm2, KIgemm2w, KIgemm2r, KDg5 };
+enum Loader {
+    LGeneric,       // the skeleton's element-wise loaders (ConvFwdALoader / K4V, ConvDgALoader, WgALoader + WgBLoader)
+    LTap,           // igemm: tap-major reduction
+    LRow4,          // igemm: the k4 s2 p1 row loaders (16-byte pieces)
+    LWgRow,         // igemm Wg: whole row segments (WgALoaderRow + WgBLoaderRow)
+    LRows2,         // igemm2: the geometry's own raw-row loaders (ConvFwdA2 / ConvDgA2)
+    LGather2,       // igemm2: ConvTapA2 / ConvDgTapA2
+    LPlane2,        // igemm2: 1x1 as a plain GEMM (PlaneA2)
+    LFewk,          // direct 3x3 kernels for <= 4 output channels
+    LSmallch,       // direct 3x3 MFMA 16x16x4 kernels
+    LSmallc,        // direct k4 s2 p1 Dg onto <= 4 channels (ks == 0: the one-position kernel)
+    LSmallc5,       // ... 5x5 s2 p2
+    LFewc           // direct k4 s2 p1 Wg with <= 4 image channels
+};
+// what the planner cannot know from the shape; `in` is what the A loader reads (x for F, y for Dg, both operands for Wg)
+struct Facts {
+    bool in16, out16, out8;      // alignment of the tensors
+    size_t ws_bytes;             // workspace available (0: none)
+    bool epilogue;               // a bias or an activation is present
+    bool stats;                  // BatchNorm statistics are requested: no direct kernel carries them
+};
+// 16-byte aligned tensors, a workspace of the advertised size, no bias / activation: what gz_conv2d_plan describes
+static const Facts kIdeal{true, true, true, ~(size_t)0, false, false};
+static Facts facts_of(const void* in, const void* out, const void* ws, size_t ws_bytes, bool epilogue, bool stats) {
+    return Facts{((uintptr_t)in & 15) == 0, ((uintptr_t)out & 15) == 0, ((uintptr_t)out & 7) == 0, ws ? ws_bytes : 0,
+                 epilogue, stats};
+}
+struct Choice {
+    Kind kind;
+    Loader loader;
+    TileId tile;
+    int splits;          // reduction splits asked of the launcher
+    int slabs;           // z-slices (workspace slabs) that gives
+    int ks, cw;          // LSmallc / LSmallc5: wavefronts sharing the channel loop; igemm2w: pixel-chunk width
+    int wave_groups;     // igemm2: 2 when the launcher runs two wave groups per workgroup
+    bool ws_short;       // the plan wanted slabs the workspace cannot hold: the unsplit fallback was taken
+};
+static Choice choice_of(Kind kind, Loader loader, TileId tile) { return Choice{kind, loader, tile, 1, 1, 0, 0, 1, false}; }
+// a split plan needs a workspace: none at all, or one smaller than `need`, and the launch runs unsplit
+static bool ws_lacks(const Facts& f, size_t need) { return f.ws_bytes == 0 || f.ws_bytes < need; }
+
 // Which launches take the igemm2 skeleton: its workgroup is a whole CU's worth of matrix pipes (one wavefront per
 // SIMD), so 256 tiles already fill the chip and anything from there up runs at the loop's rate; fewer would leave
 // CUs idle (those launches keep igemm_kernel + split-K).  256x128 tiles keep two workgroups per CU, whose prologues /
@@ -483,7 +528,7 @@ static bool too_large(long long elems) { return elems * 4 >= (1ll << 31); }
 // ---------------------------------------------------------------------------
 template <class G, class Cfg>
 static int run_fwd(const float* x, const float* wp, const float* bias, float* y, const ConvShape& s, int act,
-                   float slope, hipStream_t st, int splits = 1, float* slab = nullptr, float* stats = nullptr) {
+                   float slope, hipStream_t st, Loader ld, int splits, float* slab, float* stats) {
 #ifndef GZ_NO_K4V
     using AL = std::conditional_t<G::kh == 4 && G::kw == 4, ConvFwdALoaderK4V<Cfg::BM, G::s, G::p>,
                                   ConvFwdALoader<Cfg::BM, G::kh, G::kw, G::s, G::p>>;
@@ -496,7 +541,7 @@ static int run_fwd(const float* x, const float* wp, const float* bias, float* y,
     EpiNCHWB::Params pe{y, M, s.K, s.OH * s.OW, make_fastdiv(s.OH * s.OW), bias, act, slope,
                        reinterpret_cast<f32x2*>(stats)};
     if constexpr (BK % (G::kh * G::kw) != 0) {
-        if (fwd_tap_major(s.C, G::kh, G::kw)) {
+        if (ld == LTap) {
             using ALT = ConvFwdALoaderTap<Cfg::BM, G::kh, G::kw, G::s, G::p>;
             int Kt = G::kh * G::kw * round_bk(s.C);
             typename BL::Params pbt{wp, Kt, round4(s.K), round4(s.K), 0};
@@ -506,12 +551,7 @@ static int run_fwd(const float* x, const float* wp, const float* bias, float* y,
     int Kg = s.C * G::kh * G::kw;
     typename BL::Params pb{wp, Kg, round4(s.K), round4(s.K), 0};
     if constexpr (G::kh == 4 && G::kw == 4 && G::s == 2 && G::p == 1) {
-        const bool no_row4 = knobs().no_row4;          // experiment: the K4V loader
-        // OW >= 16 only: with shorter rows the stride-2 fragment reads of the lanes of a half-wave fall on 2*OW / 2
-        // banks (OW = 4: an 8-way conflict; measured 113 -> 108 TFLOP/s on D.block3, 122 -> 117 on G.block2's
-        // backward), where K4V's im2col image stays conflict-free; at OW = 16 / 32 it is +5 % (D.block1) or neutral
-        if (!no_row4 && s.W == 2 * s.OW && s.H == 2 * s.OH && s.OW >= 16 && s.OW <= Cfg::BM && Cfg::BM % s.OW == 0 &&
-            (((uintptr_t)x) & 15) == 0) {
+        if (ld == LRow4) {
             using AR = ConvFwdALoaderRow4<Cfg::BM>;
             return launch_igemm<Cfg, AR, BL, EpiNCHWB>(pa, pb, pe, M, s.K, Kg, 1, splits, st, slab);
         }
@@ -537,7 +577,7 @@ static int run_fwd2(const float* x, const float* wp, const float* bias, float* y
 // any other geometry whose reduction is tap-major (5x5 s2 p2, 3x3 s1 p1, 1x1 ...): gather loader, 4-byte LDS-DMA
 template <class G, class Cfg>
 static int run_fwdtap2_impl(const float* x, const float* wp, const float* bias, float* y, const ConvShape& s, int act,
-                            float slope, hipStream_t st, int splits, float* slab, float* stats) {
+                            float slope, hipStream_t st, Loader ld, int splits, float* slab, float* stats) {
     using AL = ConvTapA2<Cfg::BM, G::kh, G::kw, G::s, G::p>;
     using BL = MContigB2<Cfg::BN>;
     typename AL::Params pa{x, s, make_fastdiv(s.OH * s.OW), make_fastdiv(s.OW)};
@@ -548,7 +588,7 @@ static int run_fwdtap2_impl(const float* x, const float* wp, const float* bias, 
     // (1x1: the plain [C][K] weight image IS the tap-major one; it has no padding rows, the descriptor ends at row C)
     typename BL::Params pb{wp, G::kh * G::kw == 1 ? s.C : Kt, round4(s.K), round4(s.K), 0};
     if constexpr (G::kh * G::kw == 1 && G::s == 1 && G::p == 0) {
-        if (!knobs().no_plane_a && ((s.H * s.W) & 3) == 0 && !((uintptr_t)x & 15)) {      // plain GEMM: 16-byte pieces
+        if (ld == LPlane2) {      // plain GEMM: 16-byte pieces
             using AP = PlaneA2<Cfg::BM>;
             typename AP::Params pp{x, s.C, s.H * s.W, M, make_fastdiv(s.H * s.W)};
             return launch_igemm2<Cfg, AP, BL, EpiNCHWB>(pp, pb, pe, M, s.K, Kt, 1, splits, st, slab);
@@ -565,14 +605,14 @@ constexpr bool has_own_igemm2_loaders() { return G::kh == 4 && G::kw == 4 && G::
 
 template <class G, class Cfg>
 static int run_fwdtap2(const float* x, const float* wp, const float* bias, float* y, const ConvShape& s, int act,
-                       float slope, hipStream_t st, int splits, float* slab, float* stats) {
+                       float slope, hipStream_t st, Loader ld, int splits, float* slab, float* stats) {
     if constexpr (has_own_igemm2_loaders<G>()) return GZ_ERR_UNSUPPORTED;
-    else return run_fwdtap2_impl<G, Cfg>(x, wp, bias, y, s, act, slope, st, splits, slab, stats);
+    else return run_fwdtap2_impl<G, Cfg>(x, wp, bias, y, s, act, slope, st, ld, splits, slab, stats);
 }
 
 template <class Cfg>
 static int run_fwd2_ow(const float* x, const float* wp, const float* bias, float* y, const ConvShape& s, int act,
-                       float slope, hipStream_t st, int splits = 1, float* slab = nullptr, float* stats = nullptr) {
+                       float slope, hipStream_t st, int splits, float* slab, float* stats) {
     switch (s.OW) {
         case 4: return run_fwd2<Cfg, 4>(x, wp, bias, y, s, act, slope, st, splits, slab, stats);
         case 8: return run_fwd2<Cfg, 8>(x, wp, bias, y, s, act, slope, st, splits, slab, stats);
@@ -674,33 +714,6 @@ static SplitPlan fwd_plan(const ConvShape& s) {
 template <class G>
 static size_t fwd_ws_bytes(const ConvShape& s) {
     return split_bytes(fwd_plan<G>(s), (long long)s.N * s.OH * s.OW, s.K, fwd_kdim<G>(s), 1);
-}
-
-template <class G>
-static int dispatch_fwd(const float* x, const float* wp, const float* bias, float* y, const ConvShape& s,
-                        int act, float slope, float* ws, size_t ws_bytes, hipStream_t st) {
-    long long M = (long long)s.N * s.OH * s.OW;
-    SplitPlan sp = fwd_plan<G>(s);
-    if (sp.splits > 1 && (!ws || ws_bytes < fwd_ws_bytes<G>(s)))
-        sp = SplitPlan{pick_tile_fwd(M, s.K, s.OW, G::kh, G::kw, G::s, 0), 1};
-    float* slab = sp.splits > 1 ? ws : nullptr;
-    if (is_tile2(sp.tile) && fwd2_ok<G>(s) && (((uintptr_t)x) & 15) != 0) {
-        sp = SplitPlan{pick_tile_fwd(M, s.K, s.OW, G::kh, G::kw, G::s, 0), 1};      // unaligned tensor
-        slab = nullptr;
-    }
-    switch (sp.tile) {
-        case T256x256: return run_fwd2_ow<Cfg256x256>(x, wp, bias, y, s, act, slope, st, sp.splits, slab);
-        case T256x64:
-            if (!fwd2_ok<G>(s)) return run_fwdtap2<G, Cfg256x64>(x, wp, bias, y, s, act, slope, st, sp.splits, slab, nullptr);
-            return run_fwd2_ow<Cfg256x64>(x, wp, bias, y, s, act, slope, st, sp.splits, slab);
-        case T256x128:
-            if (!fwd2_ok<G>(s)) return run_fwdtap2<G, Cfg256x128>(x, wp, bias, y, s, act, slope, st, sp.splits, slab, nullptr);
-            return run_fwd2_ow<Cfg256x128>(x, wp, bias, y, s, act, slope, st, sp.splits, slab);
-        case T128x128: return run_fwd<G, Cfg128x128>(x, wp, bias, y, s, act, slope, st, sp.splits, slab);
-        case T128x64: return run_fwd<G, Cfg128x64>(x, wp, bias, y, s, act, slope, st, sp.splits, slab);
-        case T128x32: return run_fwd<G, Cfg128x32>(x, wp, bias, y, s, act, slope, st, sp.splits, slab);
-        default: return run_fwd<G, Cfg64x64>(x, wp, bias, y, s, act, slope, st, sp.splits, slab);
-    }
 }
 
 // ---------------------------------------------------------------------------
@@ -1060,17 +1073,16 @@ static int smallc_split(long long M4, int K) {
 
 // 5x5 s2 p2 onto <= 4 channels (HoloGAN's critic: the gradient of its first convolution with respect to the image):
 // the four-positions kernel only (rows of OW/4 lanes inside a wavefront, 16-byte aligned tensors, tap-major pack)
-static bool dgrad_direct5_ok(const float* y, const float* x, const ConvShape& s) {
+static bool dgrad_direct5_ok(const ConvShape& s) {
     const bool off = knobs().no_smallc || knobs().no_smallc5;
     return !off && s.C <= 4 && s.H == 2 * s.OH && s.W == 2 * s.OW && s.OW % 4 == 0 && 64 % (s.OW / 4) == 0 &&
-           (((uintptr_t)y | (uintptr_t)x) & 15) == 0 && dgrad_tap_major(s.K, 5, 5, 2);
+           dgrad_tap_major(s.K, 5, 5, 2);
 }
 
 template <int C>
 static int run_dgrad_smallc5(const float* y, const float* wp, const float* bias, float* x, const ConvShape& s, int act,
-                             float slope, hipStream_t st) {
+                             float slope, hipStream_t st, int ks) {
     const long long M4 = (long long)s.N * s.OH * s.OW / 4;
-    const int ks = smallc_split(M4, s.K);
     if (ks == 8)
         hipLaunchKernelGGL((dgrad_smallc4_k4s2p1_kernel<C, 8, 5>), dim3((unsigned)((M4 + 63) / 64)), dim3(512), 0, st, y, wp,
                            bias, x, s, make_fastdiv(s.OH * (s.OW / 4)), make_fastdiv(s.OW / 4), act, slope,
@@ -1086,19 +1098,23 @@ static int run_dgrad_smallc5(const float* y, const float* wp, const float* bias,
     return launch_status();
 }
 
+// the four-positions kernel: a row of OW/4 lanes must not straddle two wavefronts (the halo columns come from the
+// neighbour LANES); it also needs 16-byte aligned tensors.  GZ_SMALLC_ONE_POS: the round-1 kernel (experiment)
+static bool smallc_four_pos(const ConvShape& s) {
+    return !knobs().smallc_one_pos && s.OW % 4 == 0 && 64 % (s.OW / 4) == 0;
+}
+
+// ks = smallc_split(...): the four-positions kernel; ks = 0: the one-position kernel
 template <int C>
 static int run_dgrad_smallc(const float* y, const float* wp, const float* bias, float* x, const ConvShape& s, int act,
-                            float slope, hipStream_t st, const float* mask = nullptr, float mask_neg = 0.f) {
+                            float slope, hipStream_t st, int ks, const float* mask = nullptr, float mask_neg = 0.f) {
     long long M = (long long)s.N * s.OH * s.OW;
-    const bool one_pos = knobs().smallc_one_pos;          // experiment: the round-1 kernel
-    // a row of OW/4 lanes must not straddle two wavefronts (the halo columns come from the neighbour LANES)
-    if (!one_pos && s.OW % 4 == 0 && 64 % (s.OW / 4) == 0 && (((uintptr_t)y | (uintptr_t)x) & 15) == 0) {
+    if (ks > 0) {
         const long long M4 = M / 4;
         // few lane positions (bs 128 at 32x32: 512 wavefronts): split the channel loop over the workgroup instead
         // (0.080 -> 0.056 ms there; at bs 512 the unsplit form is 2x faster)
         // (round 3: measured crossover between bs 128 and bs 160 at 32x32 feature maps -- 32768 / 40960 lane positions;
         // bs 256: 114 -> 91 us for G's last layer without the split)
-        const int ks = smallc_split(M4, s.K);
         if (ks == 8)
             hipLaunchKernelGGL((dgrad_smallc4_k4s2p1_kernel<C, 8>), dim3((unsigned)((M4 + 63) / 64)), dim3(512), 0, st, y,
                                wp, bias, x, s, make_fastdiv(s.OH * (s.OW / 4)), make_fastdiv(s.OW / 4), act, slope, mask,
@@ -1124,7 +1140,7 @@ static int run_dgrad_smallc(const float* y, const float* wp, const float* bias, 
 // ---------------------------------------------------------------------------
 template <class G, class Cfg>
 static int run_dgrad(const float* y, const float* wp, const float* bias, float* x, const ConvShape& s, int act,
-                     float slope, hipStream_t st, int splits = 1, float* slab = nullptr, float* stats = nullptr) {
+                     float slope, hipStream_t st, Loader ld, int splits, float* slab, float* stats) {
     using AL = ConvDgALoader<Cfg::BM, G::kh, G::kw, G::s, G::p>;
     using BL = MContigLoader4<Cfg::BN>;
     using Epi = EpiPhaseB<G::s>;
@@ -1138,7 +1154,7 @@ static int run_dgrad(const float* y, const float* wp, const float* bias, float* 
                             reinterpret_cast<f32x2*>(stats),
                             (splits > 1 && slab) ? (M + 31) / 32 : ((M + Cfg::BM - 1) / Cfg::BM) * Cfg::WM};
     if constexpr (!AL::FIXED) {
-        if (dgrad_tap_major(s.K, G::kh, G::kw, G::s)) {
+        if (ld == LTap) {
             using ALT = ConvDgALoaderTap<Cfg::BM, G::kh, G::kw, G::s, G::p>;
             typename ALT::Params pat{y, s, AH, AW, make_fastdiv(AH * AW), make_fastdiv(AW)};
             const int kpad = round_bk(s.K);
@@ -1158,8 +1174,7 @@ static int run_dgrad(const float* y, const float* wp, const float* bias, float* 
         return launch_igemm<Cfg, AL, BL, Epi>(pa, pb, pe, M, s.C, Kg, G::s * G::s, splits, st, slab, pc);
     }
     if constexpr (G::kh == 4 && G::kw == 4 && G::s == 2 && G::p == 1) {
-        const bool no_row4 = knobs().no_row4;          // experiment: the per-element loader
-        if (!no_row4 && AW % 4 == 0 && (((uintptr_t)y) & 15) == 0) {
+        if (ld == LRow4) {
             using AR = ConvDgALoaderRow4<Cfg::BM, 4, 4, 2, 1>;
             return launch_igemm<Cfg, AR, BL, Epi>(pa, pb, pe, M, s.C, Kg, G::s * G::s, splits, st, slab);
         }
@@ -1170,7 +1185,7 @@ static int run_dgrad(const float* y, const float* wp, const float* bias, float* 
 // k4 s2 p1 transposed convolution on the igemm2 skeleton (row-shared A rows by LDS-DMA, packed per-phase weights)
 template <class Cfg>
 static int run_dgrad2(const float* y, const float* wp, const float* bias, float* x, const ConvShape& s, int act,
-                      float slope, hipStream_t st, float* stats = nullptr, int splits = 1, float* slab = nullptr) {
+                      float slope, hipStream_t st, int splits, float* slab, float* stats) {
     using AL = ConvDgA2<Cfg::BM>;
     using BL = MContigB2<Cfg::BN>;
     using Epi = EpiPhaseB<2>;
@@ -1193,7 +1208,7 @@ static int run_dgrad2(const float* y, const float* wp, const float* bias, float*
 // workgroups balance (unsplit, the 9-tap phase's workgroups would run 2.25x longer than the 4-tap phase's)
 template <class G, class Cfg>
 static int run_dgradtap2_impl(const float* y, const float* wp, const float* bias, float* x, const ConvShape& s, int act,
-                              float slope, hipStream_t st, int splits, float* slab) {
+                              float slope, hipStream_t st, Loader ld, int splits, float* slab) {
     using AL = ConvDgTapA2<Cfg::BM, G::kh, G::kw, G::s, G::p>;
     using BL = MContigB2<Cfg::BN>;
     using Epi = EpiPhaseB<G::s>;
@@ -1212,7 +1227,7 @@ static int run_dgradtap2_impl(const float* y, const float* wp, const float* bias
     for (int ph = 0; ph < G::s * G::s; ++ph)
         pc[ph] = dg_taps(G::kh, G::s, G::p, ph / G::s) * dg_taps(G::kw, G::s, G::p, ph % G::s) * (kpad / BK);
     if constexpr (G::kh * G::kw == 1 && G::s == 1 && G::p == 0) {
-        if (!knobs().no_plane_a && ((s.OH * s.OW) & 3) == 0 && !((uintptr_t)y & 15)) {
+        if (ld == LPlane2) {
             using AP = PlaneA2<Cfg::BM>;
             typename AP::Params pp{y, s.K, s.OH * s.OW, M, make_fastdiv(s.OH * s.OW)};
             return launch_igemm2<Cfg, AP, BL, Epi>(pp, pb, pe, M, s.C, Kt, 1, splits, st, slab, pc);
@@ -1223,9 +1238,9 @@ static int run_dgradtap2_impl(const float* y, const float* wp, const float* bias
 
 template <class G, class Cfg>
 static int run_dgradtap2(const float* y, const float* wp, const float* bias, float* x, const ConvShape& s, int act,
-                         float slope, hipStream_t st, int splits, float* slab) {
+                         float slope, hipStream_t st, Loader ld, int splits, float* slab) {
     if constexpr (has_own_igemm2_loaders<G>()) return GZ_ERR_UNSUPPORTED;     // (see run_fwdtap2)
-    else return run_dgradtap2_impl<G, Cfg>(y, wp, bias, x, s, act, slope, st, splits, slab);
+    else return run_dgradtap2_impl<G, Cfg>(y, wp, bias, x, s, act, slope, st, ld, splits, slab);
 }
 
 template <class G>
@@ -1327,7 +1342,7 @@ static size_t dgrad5_ws_bytes(const ConvShape& s) {
     return (size_t)p.nz * (size_t)s.N * s.OH * s.OW * (size_t)(4 * s.C) * 4;
 }
 using CfgQuad = TileCfg2<4, 1, 4, 2, 2>;       // four wavefronts of 64 pixels x (4 phases x 32 channels)
-static int run_dgrad5(const float* y, const float* wp, float* x, const ConvShape& s, hipStream_t st, const Dg5Plan& plan,
+static int run_dgrad5(const float* y, const float* wp, float* x, const ConvShape& s, hipStream_t st, int splits,
                       float* slab) {
     using Cfg = CfgQuad;
     using AL = ConvDg5A2<Cfg::BM>;
@@ -1339,7 +1354,7 @@ static int run_dgrad5(const float* y, const float* wp, float* x, const ConvShape
     const int M = s.N * AH * AW;
     typename Epi::Params pe{x, M, s.C, s.H, s.W, AH, AW, make_fastdiv(AH * AW), make_fastdiv(AW), nullptr, ACT_NONE, 0.f,
                             nullptr, 0};
-    return launch_igemm2<Cfg, AL, BL, Epi>(pa, pb, pe, M, 4 * s.C, 6 * s.K, 1, plan.splits, st, plan.nz > 1 ? slab : nullptr);
+    return launch_igemm2<Cfg, AL, BL, Epi>(pa, pb, pe, M, 4 * s.C, 6 * s.K, 1, splits, st, slab);
 }
 
 template <class G>
@@ -1351,9 +1366,9 @@ static bool dgrad2_ok(const ConvShape& s) {
 }
 
 template <class G>
-static bool dgrad_direct(const float* x, const ConvShape& s) {
+static bool dgrad_direct(const ConvShape& s) {          // (and an 8-byte aligned x: choose_dgrad)
     return G::kh == 4 && G::kw == 4 && G::s == 2 && G::p == 1 && s.C <= 4 && s.H == 2 * s.OH && s.W == 2 * s.OW &&
-           (((uintptr_t)x & 7) == 0) && !knobs().no_smallc;
+           !knobs().no_smallc;
 }
 
 template <class G>
@@ -1387,63 +1402,12 @@ static SplitPlan dgrad_plan(const ConvShape& s) {
 template <class G>
 static size_t dgrad_ws_bytes(const ConvShape& s) {
     constexpr int TAPS = ((G::kh + G::s - 1) / G::s) * ((G::kw + G::s - 1) / G::s);
-    if (s.H % G::s || s.W % G::s || dgrad_direct<G>(nullptr, s)) return 0;
+    if (s.H % G::s || s.W % G::s || dgrad_direct<G>(s)) return 0;
     const int kk = dgrad_tap_major(s.K, G::kh, G::kw, G::s) ? round_bk(s.K) : s.K;
     const size_t b = split_bytes(dgrad_plan<G>(s), (long long)s.N * (s.H / G::s) * (s.W / G::s), s.C, kk * TAPS, G::s * G::s);
     // (ConvDg5A2 needs aligned tensors, known only at the launch: the workspace serves either path)
     const size_t b5 = dgrad5_ws_bytes<G>(s);
     return b > b5 ? b : b5;
-}
-
-template <class G>
-static int dispatch_dgrad(const float* y, const float* wp, const float* bias, float* x, const ConvShape& s,
-                          int act, float slope, float* ws, size_t ws_bytes, hipStream_t st) {
-    if (s.H % G::s || s.W % G::s) return GZ_ERR_UNSUPPORTED;
-    if (dgrad_direct<G>(x, s)) {
-        switch (s.C) {
-            case 1: return run_dgrad_smallc<1>(y, wp, bias, x, s, act, slope, st);
-            case 2: return run_dgrad_smallc<2>(y, wp, bias, x, s, act, slope, st);
-            case 3: return run_dgrad_smallc<3>(y, wp, bias, x, s, act, slope, st);
-            default: return run_dgrad_smallc<4>(y, wp, bias, x, s, act, slope, st);
-        }
-    }
-    if constexpr (G::kh == 5 && G::kw == 5 && G::s == 2 && G::p == 2) {
-        if (dgrad_direct5_ok(y, x, s)) {
-            switch (s.C) {
-                case 1: return run_dgrad_smallc5<1>(y, wp, bias, x, s, act, slope, st);
-                case 2: return run_dgrad_smallc5<2>(y, wp, bias, x, s, act, slope, st);
-                case 3: return run_dgrad_smallc5<3>(y, wp, bias, x, s, act, slope, st);
-                default: return run_dgrad_smallc5<4>(y, wp, bias, x, s, act, slope, st);
-            }
-        }
-    }
-    long long M = (long long)s.N * (s.H / G::s) * (s.W / G::s);
-    if constexpr (G::kh == 5 && G::kw == 5 && G::s == 2 && G::p == 2) {
-        if (!bias && act == ACT_NONE && (((uintptr_t)y | (uintptr_t)x | (uintptr_t)wp) & 15) == 0) {
-            const Dg5Plan p5 = dgrad5_plan<G>(s);
-            if (p5.ok && (p5.nz <= 1 || (ws && ws_bytes >= dgrad5_ws_bytes<G>(s))))
-                return run_dgrad5(y, wp, x, s, st, p5, ws);
-        }
-    }
-    SplitPlan sp = dgrad_plan<G>(s);
-    if (sp.splits > 1 && (!ws || ws_bytes < dgrad_ws_bytes<G>(s))) sp = SplitPlan{pick_tile(M, s.C, G::s * G::s), 1};
-    float* slab = sp.splits > 1 ? ws : nullptr;
-    if (is_tile2(sp.tile) && dgrad2_ok<G>(s) && (((uintptr_t)y) & 15) != 0)
-        sp = SplitPlan{pick_tile(M, s.C, G::s * G::s), 1};        // unaligned tensor: the element-wise loaders
-    switch (sp.tile) {
-        case T256x256: return run_dgrad2<Cfg256x256>(y, wp, bias, x, s, act, slope, st);
-        case T256x128:
-            if (!dgrad2_ok<G>(s)) return run_dgradtap2<G, Cfg256x128>(y, wp, bias, x, s, act, slope, st, sp.splits, slab);
-            return run_dgrad2<Cfg256x128>(y, wp, bias, x, s, act, slope, st, nullptr, sp.splits, slab);
-        case T512x64: return run_dgrad2<Cfg512x64>(y, wp, bias, x, s, act, slope, st);
-        case T256x64:
-            if (!dgrad2_ok<G>(s)) return run_dgradtap2<G, Cfg256x64>(y, wp, bias, x, s, act, slope, st, sp.splits, slab);
-            return run_dgrad2<Cfg256x64>(y, wp, bias, x, s, act, slope, st, nullptr, sp.splits, slab);
-        case T128x128: return run_dgrad<G, Cfg128x128>(y, wp, bias, x, s, act, slope, st, sp.splits, slab);
-        case T128x64: return run_dgrad<G, Cfg128x64>(y, wp, bias, x, s, act, slope, st, sp.splits, slab);
-        case T128x32: return run_dgrad<G, Cfg128x32>(y, wp, bias, x, s, act, slope, st, sp.splits, slab);
-        default: return run_dgrad<G, Cfg64x64>(y, wp, bias, x, s, act, slope, st, sp.splits, slab);
-    }
 }
 
 // ---------------------------------------------------------------------------
@@ -1631,9 +1595,8 @@ __global__ __launch_bounds__(256) void conv3x3_fewk_kernel(const float* __restri
     }
 }
 
-static bool conv3_fewk_ok(int CI, int CO, int H, int W, const void* in, const void* out) {
-    return !knobs().no_fewk_conv && CO <= 4 && CI <= 64 && W == 64 && (H & 7) == 0 &&
-           !(((uintptr_t)in | (uintptr_t)out) & 15);
+static bool conv3_fewk_ok(int CI, int CO, int H, int W) {          // (and 16-byte aligned tensors: choose_fwd / choose_dgrad)
+    return !knobs().no_fewk_conv && CO <= 4 && CI <= 64 && W == 64 && (H & 7) == 0;
 }
 
 static bool conv3_smallch_ok(int N, int CI, int CO, int H, int W) {
@@ -1645,8 +1608,8 @@ static bool conv3_smallch_ok(int N, int CI, int CO, int H, int W) {
 }
 
 static int run_conv3_smallch(const float* in, const float* wp, const float* bias, float* out, int N, int CI, int CO,
-                             int H, int W, int tap_major, int flip, int act, float slope, hipStream_t st) {
-    if (conv3_fewk_ok(CI, CO, H, W, in, out)) {
+                             int H, int W, int tap_major, int flip, int act, float slope, hipStream_t st, Loader ld) {
+    if (ld == LFewk) {
         const dim3 grid((unsigned)(N * (H >> 3)));
 #define GZ_FEWK(KK_)                                                                                                  \
     hipLaunchKernelGGL((conv3x3_fewk_kernel<KK_>), grid, dim3(256), 0, st, in, wp, bias, out, N, CI, CO, H, tap_major, \
@@ -1924,13 +1887,13 @@ static int wgrad_smallch_blocks(const ConvShape& s) {
 }
 
 static int run_wgrad_smallch(const float* x, const float* y, float* dw, float* dbias, float* ws, size_t ws_bytes,
-                             const ConvShape& s, hipStream_t st) {
+                             const ConvShape& s, Loader ld, hipStream_t st) {
     const int blocks = wgrad_smallch_blocks(s);
     const long long count = (long long)s.K * s.C * 9;
     if (!ws || ws_bytes < (size_t)blocks * (count + s.K) * 4) return GZ_ERR_WORKSPACE;
     const long long row = count + s.K;
     const long long outs = dbias ? row : count;
-    if (wgrad_fewk_ok(s)) {
+    if (ld == LFewk) {
         const int nsl = wgrad_fewk_slices(s), per = (s.N + nsl - 1) / nsl;
         const dim3 grid((unsigned)(((s.C + 3) / 4) * (s.H >> 3) * nsl));
         switch (s.K) {
@@ -2005,36 +1968,32 @@ static bool wg_row_geom(const ConvShape& s, WgRowGeom* g) {
     return true;
 }
 
+// a split launch wants `splits` slabs of `count` floats: as many of them as the workspace holds
+static int wg_fit_splits(int splits, size_t ws_bytes, long long count) {
+    if (splits <= 1) return splits;
+    const long long max_splits = (long long)(ws_bytes / 4) / count;
+    return max_splits < 2 ? 1 : (splits > max_splits ? (int)max_splits : splits);
+}
+
+// after a weight-gradient launch that wrote nz slabs: sum them into dw (gz_conv2d_wgrad_partial: report them instead)
+static int wg_reduce(int rc, float* ws, float* dw, int nz, long long count, hipStream_t st) {
+    if (rc != GZ_OK || nz <= 1 || defer_reduce(nz, count)) return rc;
+    if (nz <= 8)
+        hipLaunchKernelGGL(reduce_few_slabs_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, st, ws, dw, nz,
+                           count);
+    else
+        hipLaunchKernelGGL(reduce_slabs_kernel, dim3((unsigned)((count + 63) / 64)), dim3(64 * RS_WAVES), 0, st, ws, dw,
+                           nz, count, count, (float*)nullptr, 0ll);
+    return launch_status();
+}
+
 template <class G, class Cfg, class AL, class BL>
-static int launch_wgrad(const typename AL::Params& pa, const typename BL::Params& pb, float* dw, float* ws,
-                        size_t ws_bytes, const ConvShape& s, int KTOT, int NTOT, hipStream_t st) {
-    long long tiles = (long long)((s.K + Cfg::BM - 1) / Cfg::BM) * ((NTOT + Cfg::BN - 1) / Cfg::BN);
-    int chunks = (KTOT + BK - 1) / BK;
-    int splits = wgrad_splits(tiles, chunks, Cfg::BM * Cfg::BN >= 128 * 128);
-    long long count = (long long)s.K * NTOT;
-    if (splits > 1) {
-        long long max_splits = (long long)(ws_bytes / 4) / count;
-        if (max_splits < 2) splits = 1;
-        else if (splits > max_splits) splits = (int)max_splits;
-    }
-    // recompute the real number of z-slices launch_igemm will use
-    int cps = (chunks + splits - 1) / splits;
-    int nz = (chunks + cps - 1) / cps;
-    float* out = nz > 1 ? ws : dw;
-    EpiRowMajorB::Params pe{out, s.K, NTOT, NTOT, count, nullptr, ACT_NONE, 0.f};
-    int rc = launch_igemm<Cfg, AL, BL, EpiRowMajorB>(pa, pb, pe, s.K, NTOT, KTOT, 1, splits, st);
-    if (rc != GZ_OK) return rc;
-    if (nz > 1) {
-        if (defer_reduce(nz, count)) return rc;
-        if (nz <= 8)
-            hipLaunchKernelGGL(reduce_few_slabs_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, st, ws, dw,
-                               nz, count);
-        else
-            hipLaunchKernelGGL(reduce_slabs_kernel, dim3((unsigned)((count + 63) / 64)), dim3(64 * RS_WAVES), 0, st, ws,
-                               dw, nz, count, count, (float*)nullptr, 0ll);
-        rc = launch_status();
-    }
-    return rc;
+static int launch_wgrad_igemm(const typename AL::Params& pa, const typename BL::Params& pb, float* dw, float* ws,
+                        const ConvShape& s, int KTOT, int NTOT, const Choice& c, hipStream_t st) {
+    const long long count = (long long)s.K * NTOT;
+    EpiRowMajorB::Params pe{c.slabs > 1 ? ws : dw, s.K, NTOT, NTOT, count, nullptr, ACT_NONE, 0.f};
+    const int rc = launch_igemm<Cfg, AL, BL, EpiRowMajorB>(pa, pb, pe, s.K, NTOT, KTOT, 1, c.splits, st);
+    return wg_reduce(rc, ws, dw, c.slabs, count, st);
 }
 
 // ---------------------------------------------------------------------------
@@ -2270,8 +2229,8 @@ static int wgrad2_splits(const ConvShape& s) {
 }
 
 template <class G, class Cfg>
-static int run_wgrad2(const float* x, const float* y, float* dw, float* ws, size_t ws_bytes, const ConvShape& s,
-                      int splits, hipStream_t st) {
+static int run_wgrad2(const float* x, const float* y, float* dw, float* ws, const ConvShape& s, const Choice& c,
+                      hipStream_t st) {
     using AL = WgALoaderRow<Cfg::BM>;
     using BL = WgBLoaderRow<Cfg::BN, G::kh, G::kw, G::s, G::p>;
     const int KTOT = s.N * s.OH * s.OW;
@@ -2281,29 +2240,9 @@ static int run_wgrad2(const float* x, const float* y, float* dw, float* ws, size
     typename AL::Params pa{y, s, rg, KTOT};
     typename BL::Params pb{x, s, rg, KTOT, NTOT};
     const long long count = (long long)s.K * NTOT;
-    if (splits > 1) {
-        long long max_splits = (long long)(ws_bytes / 4) / count;
-        if (max_splits < 2) splits = 1;
-        else if (splits > max_splits) splits = (int)max_splits;
-    }
-    const int chunks = (KTOT + BK - 1) / BK;
-    const int cps = (chunks + splits - 1) / splits;
-    const int nz = (chunks + cps - 1) / cps;
-    float* out = nz > 1 ? ws : dw;
-    EpiRowMajorB::Params pe{out, s.K, NTOT, NTOT, count, nullptr, ACT_NONE, 0.f};
-    int rc = launch_igemm2r<Cfg, AL, BL, EpiRowMajorB>(pa, pb, pe, s.K, NTOT, KTOT, splits, st);
-    if (rc != GZ_OK) return rc;
-    if (nz > 1) {
-        if (defer_reduce(nz, count)) return rc;
-        if (nz <= 8)
-            hipLaunchKernelGGL(reduce_few_slabs_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, st, ws, dw,
-                               nz, count);
-        else
-            hipLaunchKernelGGL(reduce_slabs_kernel, dim3((unsigned)((count + 63) / 64)), dim3(64 * RS_WAVES), 0, st, ws,
-                               dw, nz, count, count, (float*)nullptr, 0ll);
-        rc = launch_status();
-    }
-    return rc;
+    EpiRowMajorB::Params pe{c.slabs > 1 ? ws : dw, s.K, NTOT, NTOT, count, nullptr, ACT_NONE, 0.f};
+    const int rc = launch_igemm2r<Cfg, AL, BL, EpiRowMajorB>(pa, pb, pe, s.K, NTOT, KTOT, c.splits, st);
+    return wg_reduce(rc, ws, dw, c.slabs, count, st);
 }
 
 // ... and with both operands by LDS-DMA (igemm2w_kernel: k4 s2 p1 only, pixel rows of 4, 8 or a multiple of 16)
@@ -2319,108 +2258,302 @@ static int wgrad2w_cw_shape(const ConvShape& s) {        // pixel-chunk width of
     return cw;
 }
 
-template <class G>
-static int wgrad2w_cw(const float* x, const float* y, const ConvShape& s) {
-    if ((((uintptr_t)x) | ((uintptr_t)y)) & 15) return 0;
-    return wgrad2w_cw_shape<G>(s);
-}
-
 template <class G, int BN, int CW>
 struct wg2w_image {
     using type = std::conditional_t<G::kh == 4 && G::kw == 4, WgImgB2<BN, CW>, WgImgBG<BN, CW, G::kh, G::kw, G::s, G::p>>;
 };
 
 template <class G, class Cfg, int CW>
-static int run_wgrad2w(const float* x, const float* y, float* dw, float* ws, size_t ws_bytes, const ConvShape& s,
-                       int splits, hipStream_t st) {
+static int run_wgrad2w(const float* x, const float* y, float* dw, float* ws, const ConvShape& s, const Choice& c,
+                       hipStream_t st) {
     using BL = typename wg2w_image<G, Cfg::BN, CW>::type;
     const int KTOT = s.N * s.OH * s.OW;
     const int NTOT = s.C * G::kh * G::kw;
     Wg2Params p{x, y, s, make_fastdiv(s.OH * s.OW), make_fastdiv(s.OW)};
     const long long count = (long long)s.K * NTOT;
-    if (splits > 1) {
-        long long max_splits = (long long)(ws_bytes / 4) / count;
-        if (max_splits < 2) splits = 1;
-        else if (splits > max_splits) splits = (int)max_splits;
-    }
-    const int chunks = (KTOT + BK - 1) / BK;
-    const int cps = (chunks + splits - 1) / splits;
-    const int nz = (chunks + cps - 1) / cps;
-    float* out = nz > 1 ? ws : dw;
-    EpiRowMajorB::Params pe{out, s.K, NTOT, NTOT, count, nullptr, ACT_NONE, 0.f};
-    int rc = launch_igemm2w<Cfg, BL, EpiRowMajorB>(p, pe, s.K, NTOT, KTOT, splits, st);
-    if (rc != GZ_OK) return rc;
-    if (nz > 1) {
-        if (defer_reduce(nz, count)) return rc;
-        if (nz <= 8)
-            hipLaunchKernelGGL(reduce_few_slabs_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, st, ws, dw,
-                               nz, count);
-        else
-            hipLaunchKernelGGL(reduce_slabs_kernel, dim3((unsigned)((count + 63) / 64)), dim3(64 * RS_WAVES), 0, st, ws,
-                               dw, nz, count, count, (float*)nullptr, 0ll);
-        rc = launch_status();
-    }
-    return rc;
+    EpiRowMajorB::Params pe{c.slabs > 1 ? ws : dw, s.K, NTOT, NTOT, count, nullptr, ACT_NONE, 0.f};
+    const int rc = launch_igemm2w<Cfg, BL, EpiRowMajorB>(p, pe, s.K, NTOT, KTOT, c.splits, st);
+    return wg_reduce(rc, ws, dw, c.slabs, count, st);
 }
 
 template <class G, class Cfg>
-static int run_wgrad2w_cw(int cw, const float* x, const float* y, float* dw, float* ws, size_t ws_bytes,
-                          const ConvShape& s, int splits, hipStream_t st) {
+static int run_wgrad2w_cw(const float* x, const float* y, float* dw, float* ws, const ConvShape& s, const Choice& c,
+                          hipStream_t st) {
     if constexpr (wgrad2w_geom<G>()) {
-        switch (cw) {
-            case 4: return run_wgrad2w<G, Cfg, 4>(x, y, dw, ws, ws_bytes, s, splits, st);
-            case 8: return run_wgrad2w<G, Cfg, 8>(x, y, dw, ws, ws_bytes, s, splits, st);
-            default: return run_wgrad2w<G, Cfg, 16>(x, y, dw, ws, ws_bytes, s, splits, st);
+        switch (c.cw) {
+            case 4: return run_wgrad2w<G, Cfg, 4>(x, y, dw, ws, s, c, st);
+            case 8: return run_wgrad2w<G, Cfg, 8>(x, y, dw, ws, s, c, st);
+            default: return run_wgrad2w<G, Cfg, 16>(x, y, dw, ws, s, c, st);
         }
     }
     return GZ_ERR_UNSUPPORTED;
 }
 
 template <class G, class Cfg>
-static int run_wgrad(const float* x, const float* y, float* dw, float* ws, size_t ws_bytes, const ConvShape& s,
+static int run_wgrad(const float* x, const float* y, float* dw, float* ws, const ConvShape& s, const Choice& c,
                      hipStream_t st) {
     const int KTOT = s.N * s.OH * s.OW;
     const int NTOT = s.C * G::kh * G::kw;
-    WgRowGeom rg;
-    const bool generic_only = knobs().wg_generic;
-    if (!generic_only && wg_row_geom<G>(s, &rg)) {
+    if (c.loader == LWgRow) {
+        WgRowGeom rg;
+        wg_row_geom<G>(s, &rg);
         using AL = WgALoaderRow<Cfg::BM>;
         using BL = WgBLoaderRow<Cfg::BN, G::kh, G::kw, G::s, G::p>;
         typename AL::Params pa{y, s, rg, KTOT};
         typename BL::Params pb{x, s, rg, KTOT, NTOT};
-        return launch_wgrad<G, Cfg, AL, BL>(pa, pb, dw, ws, ws_bytes, s, KTOT, NTOT, st);
+        return launch_wgrad_igemm<G, Cfg, AL, BL>(pa, pb, dw, ws, s, KTOT, NTOT, c, st);
     }
     using AL = WgALoader<Cfg::BM>;
     using BL = WgBLoader<Cfg::BN, G::kh, G::kw, G::s, G::p>;
     typename AL::Params pa{y, s, make_fastdiv(s.OH * s.OW), KTOT};
     typename BL::Params pb{x, s, make_fastdiv(s.OH * s.OW), make_fastdiv(s.OW), KTOT, NTOT};
-    return launch_wgrad<G, Cfg, AL, BL>(pa, pb, dw, ws, ws_bytes, s, KTOT, NTOT, st);
+    return launch_wgrad_igemm<G, Cfg, AL, BL>(pa, pb, dw, ws, s, KTOT, NTOT, c, st);
 }
 
-extern "C" int gz_conv2d_tile(int op, int N, int C, int H, int W, int K, int OH, int OW, int KH, int KW, int S);
+// ---------------------------------------------------------------------------
+// The launch choice of each op, and the one function that executes it.  Every condition that selects a kernel or a
+// loader is written here and nowhere else; a new skeleton or loader is added in choose_* and in launch_*.
+// ---------------------------------------------------------------------------
+template <class G>
+constexpr bool is_k4s2p1() { return G::kh == 4 && G::kw == 4 && G::s == 2 && G::p == 1; }
+template <class G>
+constexpr bool is_k5s2p2() { return G::kh == 5 && G::kw == 5 && G::s == 2 && G::p == 2; }
+template <class G>
+constexpr bool is_k3s1p1() { return G::kh == 3 && G::kw == 3 && G::s == 1 && G::p == 1; }
+template <class G>
+constexpr bool is_k1() { return G::kh * G::kw == 1 && G::s == 1 && G::p == 0; }
+
+// the igemm2 part of a choice: slabs, and whether launch_igemm2 runs two wave groups per workgroup (its own test,
+// igemm2_use_kg2; the 1x1 plane loader has no two-group form, every other igemm2 convolution loader does)
+static void choose_igemm2(Choice& c, long long tiles, int kdim) {
+    c.kind = KIgemm2;
+    c.slabs = split_nz(kdim, c.splits);
+    const int chunks = (kdim + BK - 1) / BK, cps = (chunks + c.splits - 1) / c.splits;
+    if (c.loader != LPlane2 && (c.tile == T256x128 || c.tile == T256x64) && igemm2_use_kg2(tiles * c.slabs, cps))
+        c.wave_groups = 2;
+}
 
 template <class G>
-static int dispatch_wgrad(const float* x, const float* y, float* dw, float* ws, size_t ws_bytes,
-                          const ConvShape& s, hipStream_t st) {
-    TileId t = (TileId)gz_conv2d_tile(2, s.N, s.C, s.H, s.W, s.K, s.OH, s.OW, G::kh, G::kw, G::s);
-    if (t == T256x128 || t == T128x256) {
-        const int splits = wgrad2_splits<G>(s);
-        if (splits > 0) {
-            const int cw = wgrad2w_cw<G>(x, y, s);
-            if (cw)
-                return wgrad2_narrow(s) ? run_wgrad2w_cw<G, Cfg128x256>(cw, x, y, dw, ws, ws_bytes, s, splits, st)
-                                        : run_wgrad2w_cw<G, Cfg2Wg>(cw, x, y, dw, ws, ws_bytes, s, splits, st);
-            if constexpr (G::kh == 4 && G::kw == 4)       // unaligned tensors: the register-staged loaders
-                return wgrad2_narrow(s) ? run_wgrad2<G, Cfg128x256>(x, y, dw, ws, ws_bytes, s, splits, st)
-                                        : run_wgrad2<G, Cfg2Wg>(x, y, dw, ws, ws_bytes, s, splits, st);
-        }
-        t = T128x128;
+static Choice choose_fwd(const ConvShape& s, const Facts& f) {
+    const long long M = (long long)s.N * s.OH * s.OW;
+    SplitPlan sp = fwd_plan<G>(s);
+    // (a direct kernel keeps, as its gz_conv2d_tile label, the tile of the igemm launch it replaces)
+    if (is_k3s1p1<G>() && !f.stats && conv3_smallch_ok(s.N, s.C, s.K, s.H, s.W))
+        return choice_of(KDirect, conv3_fewk_ok(s.C, s.K, s.H, s.W) && f.in16 && f.out16 ? LFewk : LSmallch, sp.tile);
+    Choice c = choice_of(KIgemm, LGeneric, sp.tile);
+    if (sp.splits > 1 && ws_lacks(f, fwd_ws_bytes<G>(s))) {
+        c.ws_short = true;
+        sp = SplitPlan{pick_tile_fwd(M, s.K, s.OW, G::kh, G::kw, G::s, 0), 1};
     }
-    switch (t) {
-        case T128x128: return run_wgrad<G, Cfg128x128>(x, y, dw, ws, ws_bytes, s, st);
-        case T128x64: return run_wgrad<G, Cfg128x64>(x, y, dw, ws, ws_bytes, s, st);
-        case T128x32: return run_wgrad<G, Cfg128x32>(x, y, dw, ws, ws_bytes, s, st);
-        default: return run_wgrad<G, Cfg64x64>(x, y, dw, ws, ws_bytes, s, st);
+    if (is_tile2(sp.tile) && fwd2_ok<G>(s) && !f.in16)      // unaligned tensor: the element-wise loaders
+        sp = SplitPlan{pick_tile_fwd(M, s.K, s.OW, G::kh, G::kw, G::s, 0), 1};
+    c.tile = sp.tile;
+    c.splits = sp.splits;
+    if (is_tile2(c.tile)) {
+        const bool rows = fwd2_ok<G>(s);
+        c.loader = rows ? LRows2
+                   : (is_k1<G>() && !knobs().no_plane_a && ((s.H * s.W) & 3) == 0 && f.in16) ? LPlane2 : LGather2;
+        choose_igemm2(c, tile_count(c.tile, M, s.K, 1), rows ? s.C * 16 : G::kh * G::kw * round_bk(s.C));
+        return c;
+    }
+    c.slabs = split_nz(fwd_kdim<G>(s), c.splits);
+    const int bm = c.tile == T64x64 ? 64 : 128;
+    if (BK % (G::kh * G::kw) != 0 && fwd_tap_major(s.C, G::kh, G::kw)) c.loader = LTap;
+    // Row4 (GZ_NO_ROW4: the K4V loader) for OW >= 16 only: with shorter rows the stride-2 fragment reads of the lanes
+    // of a half-wave fall on 2*OW / 2 banks (OW = 4: an 8-way conflict; measured 113 -> 108 TFLOP/s on D.block3, 122 ->
+    // 117 on G.block2's backward), where K4V's im2col image stays conflict-free; at OW = 16 / 32 it is +5 % (D.block1)
+    // or neutral
+    else if (is_k4s2p1<G>() && !knobs().no_row4 && s.W == 2 * s.OW && s.H == 2 * s.OH && s.OW >= 16 && s.OW <= bm &&
+             bm % s.OW == 0 && f.in16)
+        c.loader = LRow4;
+    return c;
+}
+
+template <class G>
+static int launch_fwd(const Choice& c, const float* x, const float* wp, const float* bias, float* y, const ConvShape& s,
+                      int act, float slope, float* ws, float* stats, hipStream_t st) {
+    float* slab = c.splits > 1 ? ws : nullptr;
+    const Loader ld = c.loader;
+    if (stats && c.ws_short) return GZ_ERR_WORKSPACE;       // the stats entry points take no unsplit fallback
+    if (c.kind == KDirect) {
+        if constexpr (is_k3s1p1<G>())
+            return run_conv3_smallch(x, wp, bias, y, s.N, s.C, s.K, s.H, s.W, fwd_tap_major(s.C, 3, 3), 0, act, slope, st, ld);
+        return GZ_ERR_UNSUPPORTED;
+    }
+    switch (c.tile) {
+        case T256x256: return run_fwd2_ow<Cfg256x256>(x, wp, bias, y, s, act, slope, st, c.splits, slab, stats);
+        case T256x64:
+            if (ld != LRows2) return run_fwdtap2<G, Cfg256x64>(x, wp, bias, y, s, act, slope, st, ld, c.splits, slab, stats);
+            return run_fwd2_ow<Cfg256x64>(x, wp, bias, y, s, act, slope, st, c.splits, slab, stats);
+        case T256x128:
+            if (ld != LRows2) return run_fwdtap2<G, Cfg256x128>(x, wp, bias, y, s, act, slope, st, ld, c.splits, slab, stats);
+            return run_fwd2_ow<Cfg256x128>(x, wp, bias, y, s, act, slope, st, c.splits, slab, stats);
+        case T128x128: return run_fwd<G, Cfg128x128>(x, wp, bias, y, s, act, slope, st, ld, c.splits, slab, stats);
+        case T128x64: return run_fwd<G, Cfg128x64>(x, wp, bias, y, s, act, slope, st, ld, c.splits, slab, stats);
+        case T128x32: return run_fwd<G, Cfg128x32>(x, wp, bias, y, s, act, slope, st, ld, c.splits, slab, stats);
+        default: return run_fwd<G, Cfg64x64>(x, wp, bias, y, s, act, slope, st, ld, c.splits, slab, stats);
+    }
+}
+
+template <class G>
+static Choice choose_dgrad(const ConvShape& s, const Facts& f) {
+    const int ny = G::s * G::s;
+    const long long M = (long long)s.N * (s.H / G::s) * (s.W / G::s), M4 = (long long)s.N * s.OH * s.OW / 4;
+    if (s.H % G::s || s.W % G::s) return choice_of(KUnsupported, LGeneric, T64x64);
+    SplitPlan sp = dgrad_plan<G>(s);
+    if (!f.stats) {      // (a direct kernel keeps, as its gz_conv2d_tile label, the tile of the igemm launch it replaces)
+        if (is_k3s1p1<G>() && conv3_smallch_ok(s.N, s.K, s.C, s.H, s.W))
+            return choice_of(KDirect, conv3_fewk_ok(s.K, s.C, s.H, s.W) && f.in16 && f.out16 ? LFewk : LSmallch, sp.tile);
+        if (dgrad_direct<G>(s) && f.out8) {
+            Choice c = choice_of(KDirect, LSmallc, sp.tile);
+            c.ks = smallc_four_pos(s) && f.in16 && f.out16 ? smallc_split(M4, s.K) : 0;
+            return c;
+        }
+        if (is_k5s2p2<G>() && dgrad_direct5_ok(s) && f.in16 && f.out16) {
+            Choice c = choice_of(KDirect, LSmallc5, sp.tile);
+            c.ks = smallc_split(M4, s.K);
+            return c;
+        }
+        if (is_k5s2p2<G>() && !f.epilogue && f.in16 && f.out16) {
+            const Dg5Plan p5 = dgrad5_plan<G>(s);
+            if (p5.ok && (p5.nz <= 1 || !ws_lacks(f, dgrad5_ws_bytes<G>(s)))) {
+                Choice c = choice_of(KDg5, LRows2, T256x128P);
+                c.splits = p5.splits;
+                c.slabs = p5.nz;
+                return c;
+            }
+        }
+    }
+    Choice c = choice_of(KIgemm, LGeneric, sp.tile);
+    // (dgrad_ws_bytes is 0 for the shapes of the direct kernel: a launch that declined it still needs its slabs)
+    if (sp.splits > 1 && ws_lacks(f, dgrad_ws_bytes<G>(s))) {
+        c.ws_short = true;
+        sp = SplitPlan{pick_tile(M, s.C, ny), 1};
+    }
+    if (is_tile2(sp.tile) && dgrad2_ok<G>(s) && !f.in16)      // unaligned tensor: the element-wise loaders
+        sp = SplitPlan{pick_tile(M, s.C, ny), 1};
+    c.tile = sp.tile;
+    c.splits = sp.splits;
+    if (is_tile2(c.tile)) {
+        constexpr int TAPS = ((G::kh + G::s - 1) / G::s) * ((G::kw + G::s - 1) / G::s);
+        const bool rows = dgrad2_ok<G>(s);
+        c.loader = rows ? LRows2
+                   : (is_k1<G>() && !knobs().no_plane_a && ((s.OH * s.OW) & 3) == 0 && f.in16) ? LPlane2 : LGather2;
+        choose_igemm2(c, tile_count(c.tile, M, s.C, ny), rows ? 4 * s.K : TAPS * round_bk(s.K));
+        return c;
+    }
+    if (dgrad_tap_major(s.K, G::kh, G::kw, G::s)) c.loader = LTap;
+    else if (is_k4s2p1<G>() && !knobs().no_row4 && (s.W / 2) % 4 == 0 && f.in16) c.loader = LRow4;    // (GZ_NO_ROW4: per element)
+    return c;
+}
+
+template <class G>
+static int launch_dgrad(const Choice& c, const float* y, const float* wp, const float* bias, float* x, const ConvShape& s,
+                        int act, float slope, float* ws, float* stats, hipStream_t st) {
+    float* slab = c.splits > 1 ? ws : nullptr;
+    const Loader ld = c.loader;
+    if (c.kind == KUnsupported) return GZ_ERR_UNSUPPORTED;
+    if (stats && c.ws_short) return GZ_ERR_WORKSPACE;       // the stats entry points take no unsplit fallback
+    if (c.kind == KDg5) return run_dgrad5(y, wp, x, s, st, c.splits, c.slabs > 1 ? ws : nullptr);
+    if (c.kind == KDirect && (ld == LFewk || ld == LSmallch)) {
+        if constexpr (is_k3s1p1<G>())
+            return run_conv3_smallch(y, wp, bias, x, s.N, s.K, s.C, s.H, s.W, dgrad_tap_major(s.K, 3, 3, 1), 1, act, slope, st, ld);
+        return GZ_ERR_UNSUPPORTED;
+    }
+    if (c.kind == KDirect) {
+#define GZ_SMALLC(C_)                                                                                     \
+    return ld == LSmallc5 ? run_dgrad_smallc5<C_>(y, wp, bias, x, s, act, slope, st, c.ks)                \
+                          : run_dgrad_smallc<C_>(y, wp, bias, x, s, act, slope, st, c.ks)
+        switch (s.C) {
+            case 1: GZ_SMALLC(1);
+            case 2: GZ_SMALLC(2);
+            case 3: GZ_SMALLC(3);
+            default: GZ_SMALLC(4);
+        }
+#undef GZ_SMALLC
+    }
+    switch (c.tile) {
+        case T256x256: return run_dgrad2<Cfg256x256>(y, wp, bias, x, s, act, slope, st, 1, nullptr, stats);
+        case T256x128:
+            if (ld != LRows2) return run_dgradtap2<G, Cfg256x128>(y, wp, bias, x, s, act, slope, st, ld, c.splits, slab);
+            return run_dgrad2<Cfg256x128>(y, wp, bias, x, s, act, slope, st, c.splits, slab, stats);
+        case T512x64: return run_dgrad2<Cfg512x64>(y, wp, bias, x, s, act, slope, st, 1, nullptr, stats);
+        case T256x64:
+            if (ld != LRows2) return run_dgradtap2<G, Cfg256x64>(y, wp, bias, x, s, act, slope, st, ld, c.splits, slab);
+            return run_dgrad2<Cfg256x64>(y, wp, bias, x, s, act, slope, st, c.splits, slab, stats);
+        case T128x128: return run_dgrad<G, Cfg128x128>(y, wp, bias, x, s, act, slope, st, ld, c.splits, slab, stats);
+        case T128x64: return run_dgrad<G, Cfg128x64>(y, wp, bias, x, s, act, slope, st, ld, c.splits, slab, stats);
+        case T128x32: return run_dgrad<G, Cfg128x32>(y, wp, bias, x, s, act, slope, st, ld, c.splits, slab, stats);
+        default: return run_dgrad<G, Cfg64x64>(y, wp, bias, x, s, act, slope, st, ld, c.splits, slab, stats);
+    }
+}
+
+template <class G>
+static Choice choose_wgrad(const ConvShape& s, const Facts& f) {
+    Choice c = choice_of(KIgemm, LGeneric, T64x64);
+    const int KTOT = s.N * s.OH * s.OW, NTOT = s.C * G::kh * G::kw;
+    const long long count = (long long)s.K * NTOT;
+    // (the direct kernels keep, as their gz_conv2d_tile label, the tile of the igemm launch they replace)
+    if (NTOT <= 32) c.tile = T128x32;
+    else if (NTOT <= 64 || s.K <= 64) c.tile = s.K <= 64 ? T64x64 : T128x64;
+    // split-K supplies the parallelism; with few pixels per split (small batches) the narrower
+    // tile keeps more workgroups busy per slab byte
+    else c.tile = KTOT >= 8192 ? T128x128 : T128x64;     // round 2: 128x128 now holds 4 workgroups per CU (was 65536)
+    const int forced = forced_tile();
+    if (forced >= 0 && forced <= 3 && !(forced == T128x128 && NTOT <= 64)) c.tile = (TileId)forced;
+    if (wgrad_smallch_ok(s, G::kh, G::kw, G::s, G::p)) {
+        c.kind = KDirect;
+        c.loader = wgrad_fewk_ok(s) ? LFewk : LSmallch;
+        c.slabs = wgrad_smallch_blocks(s);
+        return c;
+    }
+    if (is_k4s2p1<G>() && wgrad_k4s2p1_fewc_ok(s) && f.ws_bytes >= (size_t)count * 4) {
+        c.kind = KDirect;
+        c.loader = LFewc;
+        c.slabs = wgrad_k4s2p1_fewc_blocks(s);
+        return c;
+    }
+    if (forced < 0 && wgrad2w_geom<G>()) {
+        // igemm2: both operands by LDS-DMA (igemm2w: raw-row image, needs H = S * OH, rows of 4 / 8 / 16k pixels and
+        // aligned tensors), or -- k4 s2 p1 only -- the register-staged row loaders (igemm2r)
+        const int splits = wgrad2_splits<G>(s);
+        c.cw = wgrad2w_cw_shape<G>(s);
+        if (splits > 0 && (c.cw || is_k4s2p1<G>())) {
+            c.kind = c.cw && f.in16 ? KIgemm2w : (is_k4s2p1<G>() ? KIgemm2r : KIgemm);
+            c.tile = c.kind == KIgemm ? T128x128 : (wgrad2_narrow(s) ? T128x256 : T256x128);
+            c.splits = splits;
+        }
+    }
+    if (c.kind == KIgemm) {
+        const int bm = c.tile == T64x64 ? 64 : 128, bn = c.tile == T128x128 ? 128 : (c.tile == T128x32 ? 32 : 64);
+        const long long tiles = (long long)((s.K + bm - 1) / bm) * ((NTOT + bn - 1) / bn);
+        c.splits = wgrad_splits(tiles, (KTOT + BK - 1) / BK, bm * bn >= 128 * 128);
+        WgRowGeom rg;
+        c.loader = !knobs().wg_generic && wg_row_geom<G>(s, &rg) ? LWgRow : LGeneric;
+    }
+    c.splits = wg_fit_splits(c.splits, f.ws_bytes, count);
+    c.slabs = split_nz(KTOT, c.splits);
+    return c;
+}
+
+template <class G>
+static int launch_wgrad(const Choice& c, const float* x, const float* y, float* dw, float* dbias, float* ws,
+                        size_t ws_bytes, const ConvShape& s, hipStream_t st) {
+    if (c.kind == KDirect && c.loader != LFewc) return run_wgrad_smallch(x, y, dw, dbias, ws, ws_bytes, s, c.loader, st);
+    if (dbias) return GZ_ERR_UNSUPPORTED;       // ask gz_conv2d_wgrad_fuses_bias first
+    if (c.kind == KDirect) return run_wgrad_k4s2p1_fewc(x, y, nullptr, ACT_NONE, 0.f, dw, ws, ws_bytes, s, st);
+    if (c.kind == KIgemm2w)
+        return wgrad2_narrow(s) ? run_wgrad2w_cw<G, Cfg128x256>(x, y, dw, ws, s, c, st)
+                                : run_wgrad2w_cw<G, Cfg2Wg>(x, y, dw, ws, s, c, st);
+    if constexpr (G::kh == 4 && G::kw == 4)       // unaligned tensors: the register-staged loaders
+        if (c.kind == KIgemm2r)
+            return wgrad2_narrow(s) ? run_wgrad2<G, Cfg128x256>(x, y, dw, ws, s, c, st)
+                                    : run_wgrad2<G, Cfg2Wg>(x, y, dw, ws, s, c, st);
+    switch (c.tile) {
+        case T128x128: return run_wgrad<G, Cfg128x128>(x, y, dw, ws, s, c, st);
+        case T128x64: return run_wgrad<G, Cfg128x64>(x, y, dw, ws, s, c, st);
+        case T128x32: return run_wgrad<G, Cfg128x32>(x, y, dw, ws, s, c, st);
+        default: return run_wgrad<G, Cfg64x64>(x, y, dw, ws, s, c, st);
     }
 }
 
@@ -2620,9 +2753,8 @@ int gz_conv2d_fwd(const float* x, const float* wpack, const float* bias, float* 
     if (!shape_ok(s, KH, KW, S, P)) return GZ_ERR_BAD_SHAPE;
     if (too_large((long long)N * C * H * W) || too_large((long long)N * K * OH * OW)) return GZ_ERR_TOO_LARGE;
     if (((uintptr_t)wpack & 15) || ((uintptr_t)y & 15)) return GZ_ERR_BAD_SHAPE;
-    if (KH == 3 && KW == 3 && S == 1 && P == 1 && conv3_smallch_ok(N, C, K, H, W))
-        return run_conv3_smallch(x, wpack, bias, y, N, C, K, H, W, fwd_tap_major(C, 3, 3), 0, act, slope, stream);
-#define CALL(G) dispatch_fwd<G>(x, wpack, bias, y, s, act, slope, workspace, ws_bytes, stream)
+    const Facts f = facts_of(x, y, workspace, ws_bytes, bias || act != ACT_NONE, false);
+#define CALL(G) launch_fwd<G>(choose_fwd<G>(s, f), x, wpack, bias, y, s, act, slope, workspace, nullptr, stream)
     GZ_GEOM_DISPATCH(CALL)
 #undef CALL
 }
@@ -2635,9 +2767,8 @@ int gz_conv2d_dgrad(const float* y, const float* wpack, const float* bias, float
     if (!shape_ok(s, KH, KW, S, P)) return GZ_ERR_BAD_SHAPE;
     if (too_large((long long)N * C * H * W) || too_large((long long)N * K * OH * OW)) return GZ_ERR_TOO_LARGE;
     if ((uintptr_t)wpack & 15) return GZ_ERR_BAD_SHAPE;
-    if (KH == 3 && KW == 3 && S == 1 && P == 1 && conv3_smallch_ok(N, K, C, H, W))
-        return run_conv3_smallch(y, wpack, bias, x, N, K, C, H, W, dgrad_tap_major(K, 3, 3, 1), 1, act, slope, stream);
-#define CALL(G) dispatch_dgrad<G>(y, wpack, bias, x, s, act, slope, workspace, ws_bytes, stream)
+    const Facts f = facts_of(y, x, workspace, ws_bytes, bias || act != ACT_NONE, false);
+#define CALL(G) launch_dgrad<G>(choose_dgrad<G>(s, f), y, wpack, bias, x, s, act, slope, workspace, nullptr, stream)
     GZ_GEOM_DISPATCH(CALL)
 #undef CALL
 }
@@ -2664,7 +2795,11 @@ size_t gz_conv2d_wgrad_workspace_bytes(int N, int C, int H, int W, int K, int OH
 
 int gz_conv2d_wgrad_fuses_bias(int N, int C, int H, int W, int K, int OH, int OW, int KH, int KW, int S, int P) {
     ConvShape s{N, C, H, W, K, OH, OW};
-    return shape_ok(s, KH, KW, S, P) && wgrad_smallch_ok(s, KH, KW, S, P) ? 1 : 0;
+    if (!shape_ok(s, KH, KW, S, P)) return 0;
+#define CALL(G) choose_wgrad<G>(s, kIdeal)
+    const Choice c = [&]() -> Choice { GZ_GEOM_DISPATCH_OR(CALL, choice_of(KUnsupported, LGeneric, T64x64)) }();
+#undef CALL
+    return c.kind == KDirect && c.loader != LFewc;
 }
 
 int gz_conv2d_wgrad(const float* x, const float* y, float* dw, float* dbias, float* workspace, size_t ws_bytes, int N,
@@ -2673,12 +2808,8 @@ int gz_conv2d_wgrad(const float* x, const float* y, float* dw, float* dbias, flo
     ConvShape s{N, C, H, W, K, OH, OW};
     if (!shape_ok(s, KH, KW, S, P)) return GZ_ERR_BAD_SHAPE;
     if (too_large((long long)N * C * H * W) || too_large((long long)N * K * OH * OW)) return GZ_ERR_TOO_LARGE;
-    if (wgrad_smallch_ok(s, KH, KW, S, P)) return run_wgrad_smallch(x, y, dw, dbias, workspace, ws_bytes, s, stream);
-    if (dbias) return GZ_ERR_UNSUPPORTED;       // ask gz_conv2d_wgrad_fuses_bias first
-    if (KH == 4 && KW == 4 && S == 2 && P == 1 && wgrad_k4s2p1_fewc_ok(s) && workspace &&
-        ws_bytes >= (size_t)K * C * 16 * 4)
-        return run_wgrad_k4s2p1_fewc(x, y, nullptr, ACT_NONE, 0.f, dw, workspace, ws_bytes, s, stream);
-#define CALL(G) dispatch_wgrad<G>(x, y, dw, workspace, ws_bytes, s, stream)
+    const Facts f = facts_of((const void*)((uintptr_t)x | (uintptr_t)y), dw, workspace, ws_bytes, false, false);
+#define CALL(G) launch_wgrad<G>(choose_wgrad<G>(s, f), x, y, dw, dbias, workspace, ws_bytes, s, stream)
     GZ_GEOM_DISPATCH(CALL)
 #undef CALL
 }
@@ -2693,18 +2824,10 @@ int gz_conv2d_wgrad_partial(const float* x, const float* y, float* dw, float* wo
     if (too_large((long long)N * C * H * W) || too_large((long long)N * K * OH * OW)) return GZ_ERR_TOO_LARGE;
     *nz_out = 1;
     *stride_out = (long long)K * C * KH * KW;
-    if (wgrad_smallch_ok(s, KH, KW, S, P)) return run_wgrad_smallch(x, y, dw, nullptr, workspace, ws_bytes, s, stream);
-    WgDefer d{1, *stride_out};
+    const Facts f = facts_of((const void*)((uintptr_t)x | (uintptr_t)y), dw, workspace, ws_bytes, false, false);
+    WgDefer d{1, *stride_out};       // (the 3x3 direct kernels reduce their own slabs and leave it alone)
     tl_wg_defer = &d;
-    if (KH == 4 && KW == 4 && S == 2 && P == 1 && wgrad_k4s2p1_fewc_ok(s) && workspace &&
-        ws_bytes >= (size_t)K * C * 16 * 4) {
-        const int rc = run_wgrad_k4s2p1_fewc(x, y, nullptr, ACT_NONE, 0.f, dw, workspace, ws_bytes, s, stream);
-        tl_wg_defer = nullptr;
-        *nz_out = d.nz;
-        *stride_out = d.stride;
-        return rc;
-    }
-#define CALL(G) dispatch_wgrad<G>(x, y, dw, workspace, ws_bytes, s, stream)
+#define CALL(G) launch_wgrad<G>(choose_wgrad<G>(s, f), x, y, dw, nullptr, workspace, ws_bytes, s, stream)
     const int rc = [&]() -> int { GZ_GEOM_DISPATCH(CALL) }();
 #undef CALL
     tl_wg_defer = nullptr;
@@ -2714,8 +2837,8 @@ int gz_conv2d_wgrad_partial(const float* x, const float* y, float* dw, float* wo
 }
 
 static bool dgrad_act_direct(const ConvShape& s, int KH, int KW, int S, int P, int act) {
-    return KH == 4 && KW == 4 && S == 2 && P == 1 && (act == ACT_RELU || act == ACT_LRELU) && !knobs().smallc_one_pos &&
-           !knobs().no_act_fuse && dgrad_direct<G4421>(nullptr, s) && s.OW % 4 == 0 && 64 % (s.OW / 4) == 0;
+    return KH == 4 && KW == 4 && S == 2 && P == 1 && (act == ACT_RELU || act == ACT_LRELU) && !knobs().no_act_fuse &&
+           dgrad_direct<G4421>(s) && smallc_four_pos(s);
 }
 
 int gz_conv2d_dgrad_act_fuses(int N, int C, int H, int W, int K, int OH, int OW, int KH, int KW, int S, int P, int act) {
@@ -2732,11 +2855,12 @@ int gz_conv2d_dgrad_act(const float* gy, const float* fwd_out, int act, float sl
     if (!dgrad_act_direct(s, KH, KW, S, P, act) || (((uintptr_t)gy | (uintptr_t)x | (uintptr_t)fwd_out | (uintptr_t)wpack) & 15))
         return GZ_ERR_UNSUPPORTED;
     const float neg = act == ACT_RELU ? 0.f : slope;
+    const int ks = smallc_split((long long)N * OH * OW / 4, K);
     switch (C) {
-        case 1: return run_dgrad_smallc<1>(gy, wpack, nullptr, x, s, ACT_NONE, 0.f, stream, fwd_out, neg);
-        case 2: return run_dgrad_smallc<2>(gy, wpack, nullptr, x, s, ACT_NONE, 0.f, stream, fwd_out, neg);
-        case 3: return run_dgrad_smallc<3>(gy, wpack, nullptr, x, s, ACT_NONE, 0.f, stream, fwd_out, neg);
-        default: return run_dgrad_smallc<4>(gy, wpack, nullptr, x, s, ACT_NONE, 0.f, stream, fwd_out, neg);
+        case 1: return run_dgrad_smallc<1>(gy, wpack, nullptr, x, s, ACT_NONE, 0.f, stream, ks, fwd_out, neg);
+        case 2: return run_dgrad_smallc<2>(gy, wpack, nullptr, x, s, ACT_NONE, 0.f, stream, ks, fwd_out, neg);
+        case 3: return run_dgrad_smallc<3>(gy, wpack, nullptr, x, s, ACT_NONE, 0.f, stream, ks, fwd_out, neg);
+        default: return run_dgrad_smallc<4>(gy, wpack, nullptr, x, s, ACT_NONE, 0.f, stream, ks, fwd_out, neg);
     }
 }
 
@@ -2836,8 +2960,9 @@ static int stats_tm_rows(TileId t, long long M) {       // partial rows per phas
 int gz_conv2d_fwd_stats_rows(int N, int C, int H, int W, int K, int OH, int OW, int KH, int KW, int S, int P) {
     ConvShape s{N, C, H, W, K, OH, OW};
     if (!shape_ok(s, KH, KW, S, P)) return 0;
-#define CALL(G) fwd_plan<G>(s)
-    SplitPlan sp = [&]() -> SplitPlan { GZ_GEOM_DISPATCH_OR(CALL, (SplitPlan{T64x64, 2})) }();
+    const Facts f{true, true, true, kIdeal.ws_bytes, false, true};
+#define CALL(G) choose_fwd<G>(s, f)
+    const Choice sp = [&]() -> Choice { GZ_GEOM_DISPATCH_OR(CALL, (Choice{KIgemm, LGeneric, T64x64, 2})) }();
 #undef CALL
     // split launches (round 4): splitk_finish_kernel runs the same epilogue per 32 x 32 output block and writes the
     // statistics there -- one partial row per 32 pixels
@@ -2854,25 +2979,8 @@ int gz_conv2d_fwd_stats_ws(const float* x, const float* wpack, float* y, float* 
     if (gz_conv2d_fwd_stats_rows(N, C, H, W, K, OH, OW, KH, KW, S, P) <= 0) return GZ_ERR_UNSUPPORTED;
     if ((((uintptr_t)x | (uintptr_t)y) & 15) != 0) return GZ_ERR_BAD_SHAPE;      // 16-byte LDS-DMA pieces / row stores
     if (too_large((long long)N * C * H * W) || too_large((long long)N * K * OH * OW)) return GZ_ERR_TOO_LARGE;
-#define CALL(G)                                                                                                      \
-    [&]() -> int {                                                                                                   \
-        const SplitPlan sp = fwd_plan<G>(s);                                                                         \
-        if (sp.splits > 1 && (!workspace || ws_bytes < fwd_ws_bytes<G>(s))) return GZ_ERR_WORKSPACE;                 \
-        float* slab = sp.splits > 1 ? workspace : nullptr;                                                           \
-        switch (sp.tile) {                                                                                           \
-            case T256x256: return run_fwd2_ow<Cfg256x256>(x, wpack, nullptr, y, s, 0, 0.f, stream, sp.splits, slab, stats); \
-            case T256x64:                                                                                            \
-                if (!fwd2_ok<G>(s)) return run_fwdtap2<G, Cfg256x64>(x, wpack, nullptr, y, s, 0, 0.f, stream, sp.splits, slab, stats); \
-                return run_fwd2_ow<Cfg256x64>(x, wpack, nullptr, y, s, 0, 0.f, stream, sp.splits, slab, stats);      \
-            case T256x128:                                                                                           \
-                if (!fwd2_ok<G>(s)) return run_fwdtap2<G, Cfg256x128>(x, wpack, nullptr, y, s, 0, 0.f, stream, sp.splits, slab, stats); \
-                return run_fwd2_ow<Cfg256x128>(x, wpack, nullptr, y, s, 0, 0.f, stream, sp.splits, slab, stats);     \
-            case T128x128: return run_fwd<G, Cfg128x128>(x, wpack, nullptr, y, s, 0, 0.f, stream, sp.splits, slab, stats); \
-            case T128x64: return run_fwd<G, Cfg128x64>(x, wpack, nullptr, y, s, 0, 0.f, stream, sp.splits, slab, stats);   \
-            case T128x32: return run_fwd<G, Cfg128x32>(x, wpack, nullptr, y, s, 0, 0.f, stream, sp.splits, slab, stats);   \
-            default: return run_fwd<G, Cfg64x64>(x, wpack, nullptr, y, s, 0, 0.f, stream, sp.splits, slab, stats);         \
-        }                                                                                                            \
-    }()
+    const Facts f = facts_of(x, y, workspace, ws_bytes, false, true);
+#define CALL(G) launch_fwd<G>(choose_fwd<G>(s, f), x, wpack, nullptr, y, s, 0, 0.f, workspace, stats, stream)
     GZ_GEOM_DISPATCH(CALL)
 #undef CALL
 }
@@ -2885,8 +2993,9 @@ int gz_conv2d_fwd_stats(const float* x, const float* wpack, float* y, float* sta
 int gz_conv2d_dgrad_stats_rows(int N, int C, int H, int W, int K, int OH, int OW, int KH, int KW, int S, int P) {
     ConvShape s{N, C, H, W, K, OH, OW};
     if (!shape_ok(s, KH, KW, S, P) || H % S || W % S) return 0;
-#define CALL(G) (dgrad_direct<G>(nullptr, s) ? SplitPlan{T64x64, 2} : dgrad_plan<G>(s))
-    SplitPlan sp = [&]() -> SplitPlan { GZ_GEOM_DISPATCH_OR(CALL, (SplitPlan{T64x64, 2})) }();
+    const Facts f{true, true, true, kIdeal.ws_bytes, false, true};
+#define CALL(G) (dgrad_direct<G>(s) ? Choice{KIgemm, LGeneric, T64x64, 2} : choose_dgrad<G>(s, f))
+    const Choice sp = [&]() -> Choice { GZ_GEOM_DISPATCH_OR(CALL, (Choice{KIgemm, LGeneric, T64x64, 2})) }();
 #undef CALL
     if (is_tile2(sp.tile) && !(KH == 4 && KW == 4 && S == 2 && P == 1)) return 0;      // gather-loader launches: not fused
     if (sp.splits > 1) {          // the finish kernel writes them, one partial row per 32 pixels of a phase (round 4)
@@ -2905,22 +3014,8 @@ int gz_conv2d_dgrad_stats_ws(const float* y, const float* wpack, float* x, float
     if (gz_conv2d_dgrad_stats_rows(N, C, H, W, K, OH, OW, KH, KW, S, P) <= 0) return GZ_ERR_UNSUPPORTED;
     if ((((uintptr_t)x | (uintptr_t)y) & 15) != 0) return GZ_ERR_BAD_SHAPE;      // 16-byte LDS-DMA pieces / row stores
     if (too_large((long long)N * C * H * W) || too_large((long long)N * K * OH * OW)) return GZ_ERR_TOO_LARGE;
-#define CALL(G)                                                                                                        \
-    [&]() -> int {                                                                                                     \
-        const SplitPlan sp = dgrad_plan<G>(s);                                                                         \
-        if (sp.splits > 1 && (!workspace || ws_bytes < dgrad_ws_bytes<G>(s))) return GZ_ERR_WORKSPACE;                 \
-        float* slab = sp.splits > 1 ? workspace : nullptr;                                                             \
-        switch (sp.tile) {                                                                                             \
-            case T256x256: return run_dgrad2<Cfg256x256>(y, wpack, nullptr, x, s, 0, 0.f, stream, stats);               \
-            case T256x128: return run_dgrad2<Cfg256x128>(y, wpack, nullptr, x, s, 0, 0.f, stream, stats, sp.splits, slab); \
-            case T512x64: return run_dgrad2<Cfg512x64>(y, wpack, nullptr, x, s, 0, 0.f, stream, stats);                 \
-            case T256x64: return run_dgrad2<Cfg256x64>(y, wpack, nullptr, x, s, 0, 0.f, stream, stats, sp.splits, slab); \
-            case T128x128: return run_dgrad<G, Cfg128x128>(y, wpack, nullptr, x, s, 0, 0.f, stream, sp.splits, slab, stats); \
-            case T128x64: return run_dgrad<G, Cfg128x64>(y, wpack, nullptr, x, s, 0, 0.f, stream, sp.splits, slab, stats);   \
-            case T128x32: return run_dgrad<G, Cfg128x32>(y, wpack, nullptr, x, s, 0, 0.f, stream, sp.splits, slab, stats);   \
-            default: return run_dgrad<G, Cfg64x64>(y, wpack, nullptr, x, s, 0, 0.f, stream, sp.splits, slab, stats);         \
-        }                                                                                                              \
-    }()
+    const Facts f = facts_of(y, x, workspace, ws_bytes, false, true);
+#define CALL(G) launch_dgrad<G>(choose_dgrad<G>(s, f), y, wpack, nullptr, x, s, 0, 0.f, workspace, stats, stream)
     GZ_GEOM_DISPATCH(CALL)
 #undef CALL
 }
@@ -3002,66 +3097,17 @@ int gz_debug_read_stamps(void* out, int nwg) {
 }
 #endif
 
-/* which tile configuration a launch of op (0 F, 1 Dg, 2 Wg) would use: 0 128x128, 1 128x64, 2 128x32, 3 64x64 */
+/* which tile configuration a launch of op (0 F, 1 Dg, 2 Wg) would use, a TileId: 0 128x128, 1 128x64, 2 128x32,
+ * 3 64x64, 4.. the igemm2 tiles.  A label for timers: the tile of the launch's choice for ideal facts.  The call has
+ * no padding argument (the four geometries differ in their kernel size); a shape or geometry that no launch exists
+ * for gets 3. */
 int gz_conv2d_tile(int op, int N, int C, int H, int W, int K, int OH, int OW, int KH, int KW, int S) {
-    // (the reduction lengths below ignore the channel padding of the tap-major loaders: labels only)
-    if (op == 0) {
-        if (KH == 4 && KW == 4 && S == 2) {
-            ConvShape s{N, C, H, W, K, OH, OW};
-            const SplitPlan p2 = fwd2_plan<G4421>(s);
-            if (p2.tile == T256x256 || p2.tile == T256x128 || p2.tile == T256x64) return p2.tile;
-        }
-        if ((KH == 5 && KW == 5 && S == 2) || (KH == 3 && KW == 3 && S == 1) || (KH == 1 && KW == 1 && S == 1)) {
-            ConvShape s{N, C, H, W, K, OH, OW};
-            const SplitPlan p2 = KH == 5 ? fwdtap2_plan<G5522>(s) : KH == 3 ? fwdtap2_plan<G3311>(s) : fwdtap2_plan<G1110>(s);
-            if (p2.tile == T256x128 || p2.tile == T256x64) return p2.tile;
-        }
-        return pick_tile_fwd((long long)N * OH * OW, K, OW, KH, KW, S, C * KH * KW);
-    }
-    if (op == 1) {
-        if (KH == 4 && KW == 4 && S == 2) {
-            ConvShape s{N, C, H, W, K, OH, OW};
-            if (dgrad2_ok<G4421>(s) && !dgrad_direct<G4421>(nullptr, s)) {
-                const SplitPlan sp = dgrad_plan<G4421>(s);
-                if (is_tile2(sp.tile)) return sp.tile;
-            }
-        }
-        if (KH == 5 && KW == 5 && S == 2) {
-            ConvShape s{N, C, H, W, K, OH, OW};
-            if (dgrad5_plan<G5522>(s).ok) return T256x128P;
-        }
-        if ((KH == 5 && KW == 5 && S == 2) || (KH == 3 && KW == 3 && S == 1) || (KH == 1 && KW == 1 && S == 1)) {
-            ConvShape s{N, C, H, W, K, OH, OW};
-            const SplitPlan pt = KH == 5 ? dgradtap2_plan<G5522>(s) : KH == 3 ? dgradtap2_plan<G3311>(s) : dgradtap2_plan<G1110>(s);
-            if (pt.tile == T256x128 || pt.tile == T256x64) return pt.tile;
-        }
-        return pick_tile((long long)N * (H / S) * (W / S), C, S * S, K * ((KH + S - 1) / S) * ((KW + S - 1) / S));
-    }
-    long long NTOT = (long long)C * KH * KW;
-    int t;
-    if (KH == 4 && KW == 4 && S == 2 && forced_tile() < 0) {
-        ConvShape s{N, C, H, W, K, OH, OW};
-        if (wgrad2_splits<G4421>(s) > 0) return wgrad2_narrow(s) ? T128x256 : T256x128;
-    }
-    if (((KH == 5 && KW == 5 && S == 2) || (KH == 3 && KW == 3 && S == 1)) && forced_tile() < 0) {
-        // the LDS-DMA weight gradient with the generic raw-row image (needs H = S * OH, rows of 4 / 8 / 16k pixels)
-        ConvShape s{N, C, H, W, K, OH, OW};
-        const bool shape_ok = H == S * OH && W == S * OW && (W & 3) == 0 && (OW == 4 || OW == 8 || OW % 16 == 0) &&
-                              !knobs().no_igemm2w && !knobs().no_igemm2wg;
-        const int sp = !shape_ok ? 0 : KH == 5 ? wgrad2_splits<G5522>(s) : wgrad2_splits<G3311>(s);
-        if (sp > 0) return wgrad2_narrow(s) ? T128x256 : T256x128;
-    }
-    if (NTOT <= 32) t = T128x32;
-    else if (NTOT <= 64 || K <= 64) t = (K <= 64 ? T64x64 : T128x64);
-    else {
-        // split-K supplies the parallelism; with few pixels per split (small batches) the narrower
-        // tile keeps more workgroups busy per slab byte
-        long long pixels = (long long)N * OH * OW;
-        t = pixels >= 8192 ? T128x128 : T128x64;     // round 2: 128x128 now holds 4 workgroups per CU (was 65536)
-    }
-    int f = forced_tile();
-    if (f >= 0 && f <= 3 && !(f == T128x128 && NTOT <= 64)) t = f;
-    return t;
+    const int P = KH == 5 ? 2 : KH == 1 ? 0 : 1;
+    ConvShape s{N, C, H, W, K, OH, OW};
+    if (!shape_ok(s, KH, KW, S, P)) return T64x64;
+#define CALL(G) (op == 0 ? choose_fwd<G>(s, kIdeal) : op == 1 ? choose_dgrad<G>(s, kIdeal) : choose_wgrad<G>(s, kIdeal)).tile
+    GZ_GEOM_DISPATCH_OR(CALL, T64x64)
+#undef CALL
 }
 
 /* ---- which kernel a launch takes, as text (round 4: the dispatch is pinned by tests/test_dispatch_plan.py) ---------
@@ -3084,116 +3130,59 @@ static const char* tile_text(TileId t) {
     }
 }
 
-// does this igemm2 launch run two wave groups per workgroup (gz_igemm.h: igemm2_use_kg2)?  The launcher's own arithmetic.
-static bool kg2_applies(TileId t, long long M, long long N, int ny, int kdim, int splits, bool rows_loader) {
-    if (!rows_loader || !(t == T256x128 || t == T256x64)) return false;
-    const int chunks = (kdim + BK - 1) / BK;
-    const int cps = (chunks + (splits < 1 ? 1 : splits) - 1) / (splits < 1 ? 1 : splits);
-    const int nz = (chunks + cps - 1) / cps;
-    return igemm2_use_kg2(tile_count(t, M, N, ny) * nz, cps);
-}
-
 template <class G>
 static int describe_fwd(const ConvShape& s, char* b, size_t n) {
-    if (G::kh == 3 && G::kw == 3 && G::s == 1 && G::p == 1 && conv3_smallch_ok(s.N, s.C, s.K, s.H, s.W))
-        return snprintf(b, n, "F direct %s", (!knobs().no_fewk_conv && s.K <= 4 && s.C <= 64 && s.W == 64 && (s.H & 7) == 0)
-                                                 ? "conv3x3_fewk<fma>" : "conv3x3_smallch<mfma16x16x4>");
-    const SplitPlan sp = fwd_plan<G>(s);
+    const Choice c = choose_fwd<G>(s, kIdeal);
+    if (c.kind == KDirect)
+        return snprintf(b, n, "F direct %s", c.loader == LFewk ? "conv3x3_fewk<fma>" : "conv3x3_smallch<mfma16x16x4>");
     const int rows = gz_conv2d_fwd_stats_rows(s.N, s.C, s.H, s.W, s.K, s.OH, s.OW, G::kh, G::kw, G::s, G::p);
-    if (is_tile2(sp.tile)) {
-        const bool rowsA = fwd2_ok<G>(s);
-        const int kdim = rowsA ? s.C * 16 : G::kh * G::kw * round_bk(s.C);
-        // (the 1x1 plane loader has no two-group form; every other igemm2 forward loader does)
-        const bool plane = !rowsA && G::kh * G::kw == 1 && G::s == 1 && G::p == 0 && !knobs().no_plane_a && ((s.H * s.W) & 3) == 0;
-        const bool kg2 = kg2_applies(sp.tile, (long long)s.N * s.OH * s.OW, s.K, 1, kdim, sp.splits, !plane);
-        return snprintf(b, n, "F igemm2<%s> %s slabs=%d bn_stats_rows=%d%s", tile_text(sp.tile),
-                        rowsA ? "ConvFwdA2(raw rows, LDS-DMA 16B)" : "ConvTapA2(gather, LDS-DMA 4B)",
-                        split_nz(kdim, sp.splits), rows, kg2 ? " wave_groups=2" : "");
-    }
-    const char* loader = "ConvFwdALoader";
-    const int bm = sp.tile == T64x64 ? 64 : 128;
-    if (BK % (G::kh * G::kw) != 0 && fwd_tap_major(s.C, G::kh, G::kw)) loader = "ConvFwdALoaderTap";
-    else if (G::kh == 4 && G::kw == 4 && G::s == 2 && G::p == 1)
-        loader = (!knobs().no_row4 && s.W == 2 * s.OW && s.H == 2 * s.OH && s.OW >= 16 && s.OW <= bm && bm % s.OW == 0)
-                     ? "ConvFwdALoaderRow4" : "ConvFwdALoaderK4V";
-    return snprintf(b, n, "F igemm<%s> %s slabs=%d bn_stats_rows=%d", tile_text(sp.tile), loader,
-                    split_nz(fwd_kdim<G>(s), sp.splits), rows);
+    if (c.kind == KIgemm2)      // (PlaneA2 launches are described by the gather loader they stand in for)
+        return snprintf(b, n, "F igemm2<%s> %s slabs=%d bn_stats_rows=%d%s", tile_text(c.tile),
+                        c.loader == LRows2 ? "ConvFwdA2(raw rows, LDS-DMA 16B)" : "ConvTapA2(gather, LDS-DMA 4B)", c.slabs,
+                        rows, c.wave_groups == 2 ? " wave_groups=2" : "");
+    return snprintf(b, n, "F igemm<%s> %s slabs=%d bn_stats_rows=%d", tile_text(c.tile),
+                    c.loader == LTap ? "ConvFwdALoaderTap" : c.loader == LRow4 ? "ConvFwdALoaderRow4"
+                    : is_k4s2p1<G>() ? "ConvFwdALoaderK4V" : "ConvFwdALoader", c.slabs, rows);
 }
 
 template <class G>
 static int describe_dgrad(const ConvShape& s, char* b, size_t n) {
-    if (s.H % G::s || s.W % G::s) return snprintf(b, n, "Dg unsupported (H, W not multiples of the stride)");
-    if (G::kh == 3 && G::kw == 3 && G::s == 1 && G::p == 1 && conv3_smallch_ok(s.N, s.K, s.C, s.H, s.W))
-        return snprintf(b, n, "Dg direct conv3x3_smallch<mfma16x16x4>");
-    const long long M = (long long)s.N * s.OH * s.OW;
-    if (dgrad_direct<G>(nullptr, s)) {
-        if (!knobs().smallc_one_pos && s.OW % 4 == 0 && 64 % (s.OW / 4) == 0)
-            return snprintf(b, n, "Dg direct dgrad_smallc4_k4s2p1<C=%d,KS=%d>", s.C, smallc_split(M / 4, s.K));
-        return snprintf(b, n, "Dg direct dgrad_smallc_k4s2p1<C=%d>", s.C);
-    }
-    if (G::kh == 5 && G::kw == 5 && G::s == 2 && G::p == 2 && dgrad_direct5_ok(nullptr, nullptr, s))
-        return snprintf(b, n, "Dg direct dgrad_smallc4_k5s2p2<C=%d,KS=%d>", s.C, smallc_split(M / 4, s.K));
-    if constexpr (G::kh == 5 && G::kw == 5 && G::s == 2 && G::p == 2) {
-        const Dg5Plan p5 = dgrad5_plan<G>(s);
-        if (p5.ok)
-            return snprintf(b, n, "Dg igemm2<256x(4 phases x 32)> ConvDg5A2(row-shared, LDS-DMA 16B, 12 k-steps) slabs=%d "
-                                  "(no bias / activation, aligned tensors; else the gather loader)", p5.nz);
-    }
-    constexpr int TAPS = ((G::kh + G::s - 1) / G::s) * ((G::kw + G::s - 1) / G::s);
-    const SplitPlan sp = dgrad_plan<G>(s);
+    const Choice c = choose_dgrad<G>(s, kIdeal);
+    if (c.kind == KUnsupported) return snprintf(b, n, "Dg unsupported (H, W not multiples of the stride)");
+    if (c.kind == KDirect && c.loader == LSmallc5)
+        return snprintf(b, n, "Dg direct dgrad_smallc4_k5s2p2<C=%d,KS=%d>", s.C, c.ks);
+    if (c.kind == KDirect && c.loader == LSmallc && c.ks > 0)
+        return snprintf(b, n, "Dg direct dgrad_smallc4_k4s2p1<C=%d,KS=%d>", s.C, c.ks);
+    if (c.kind == KDirect && c.loader == LSmallc) return snprintf(b, n, "Dg direct dgrad_smallc_k4s2p1<C=%d>", s.C);
+    if (c.kind == KDirect) return snprintf(b, n, "Dg direct conv3x3_smallch<mfma16x16x4>");      // (either 3x3 kernel)
+    if (c.kind == KDg5)
+        return snprintf(b, n, "Dg igemm2<256x(4 phases x 32)> ConvDg5A2(row-shared, LDS-DMA 16B, 12 k-steps) slabs=%d "
+                              "(no bias / activation, aligned tensors; else the gather loader)", c.slabs);
     const int rows = gz_conv2d_dgrad_stats_rows(s.N, s.C, s.H, s.W, s.K, s.OH, s.OW, G::kh, G::kw, G::s, G::p);
-    const bool tapm = dgrad_tap_major(s.K, G::kh, G::kw, G::s);
-    const int kk = tapm ? round_bk(s.K) : s.K;
-    if (is_tile2(sp.tile)) {
-        const bool rowsA = dgrad2_ok<G>(s);
-        constexpr int TYX = ((G::kh + G::s - 1) / G::s) * ((G::kw + G::s - 1) / G::s);
-        const bool plane = !rowsA && G::kh * G::kw == 1 && G::s == 1 && G::p == 0 && !knobs().no_plane_a && ((s.OH * s.OW) & 3) == 0;
-        const bool kg2 = kg2_applies(sp.tile, (long long)s.N * (s.H / G::s) * (s.W / G::s), s.C, G::s * G::s,
-                                     rowsA ? 4 * s.K : TYX * round_bk(s.K), sp.splits, !plane);
-        return snprintf(b, n, "Dg igemm2<%s> %s splits=%d bn_stats_rows=%d%s", tile_text(sp.tile),
-                        rowsA ? "ConvDgA2(row-shared, LDS-DMA 16B)" : "ConvDgTapA2(gather, LDS-DMA 4B)", sp.splits, rows,
-                        kg2 ? " wave_groups=2" : "");
-    }
-    const char* loader = "ConvDgALoader";
-    if (tapm && !(G::kh % G::s == 0 && G::kw % G::s == 0 && BK % TAPS == 0)) loader = "ConvDgALoaderTap";
-    else if (G::kh == 4 && G::kw == 4 && G::s == 2 && G::p == 1 && !knobs().no_row4 && (s.W / 2) % 4 == 0)
-        loader = "ConvDgALoaderRow4";
-    return snprintf(b, n, "Dg igemm<%s> %s splits=%d bn_stats_rows=%d", tile_text(sp.tile), loader,
-                    sp.splits > 1 ? sp.splits : 1, rows);
-    (void)kk;
+    if (c.kind == KIgemm2)
+        return snprintf(b, n, "Dg igemm2<%s> %s splits=%d bn_stats_rows=%d%s", tile_text(c.tile),
+                        c.loader == LRows2 ? "ConvDgA2(row-shared, LDS-DMA 16B)" : "ConvDgTapA2(gather, LDS-DMA 4B)",
+                        c.splits, rows, c.wave_groups == 2 ? " wave_groups=2" : "");
+    return snprintf(b, n, "Dg igemm<%s> %s splits=%d bn_stats_rows=%d", tile_text(c.tile),
+                    c.loader == LTap ? "ConvDgALoaderTap" : c.loader == LRow4 ? "ConvDgALoaderRow4" : "ConvDgALoader",
+                    c.splits, rows);
 }
 
 template <class G>
 static int describe_wgrad(const ConvShape& s, char* b, size_t n) {
-    if (wgrad_smallch_ok(s, G::kh, G::kw, G::s, G::p))
-        return snprintf(b, n, "Wg direct %s slabs=%d", wgrad_fewk_ok(s) ? "wgrad_k3_fewk<fma>" : "wgrad_smallch_k3<mfma16x16x4>",
-                        wgrad_smallch_blocks(s));
-    if (G::kh == 4 && G::kw == 4 && G::s == 2 && G::p == 1 && wgrad_k4s2p1_fewc_ok(s))
-        return snprintf(b, n, "Wg direct wgrad_k4s2p1_fewc<mfma16x16x4,C=%d,KT=%d> slabs=%d", s.C, s.K / 16,
-                        wgrad_k4s2p1_fewc_blocks(s));
-    TileId t = (TileId)gz_conv2d_tile(2, s.N, s.C, s.H, s.W, s.K, s.OH, s.OW, G::kh, G::kw, G::s);
-    const int chunks = (s.N * s.OH * s.OW + BK - 1) / BK;
-    const int NTOT = s.C * G::kh * G::kw;
-    if (t == T256x128 || t == T128x256) {
-        const int splits = wgrad2_splits<G>(s);
-        if (splits > 0) {
-            const int cw = wgrad2w_cw_shape<G>(s);
-            const int cps = (chunks + splits - 1) / splits, nz = (chunks + cps - 1) / cps;
-            if (cw)
-                return snprintf(b, n, "Wg igemm2w<%s> %s<CW=%d>(both operands LDS-DMA) slabs=%d", tile_text(t),
-                                (G::kh == 4 && G::kw == 4) ? "WgImgB2" : "WgImgBG", cw, nz);
-            if (G::kh == 4 && G::kw == 4)
-                return snprintf(b, n, "Wg igemm2r<%s> WgALoaderRow+WgBLoaderRow(register-staged) slabs=%d", tile_text(t), nz);
-        }
-        t = T128x128;
-    }
-    const int bm = t == T64x64 ? 64 : 128, bn = t == T128x128 ? 128 : (t == T128x32 ? 32 : 64);
-    const long long tiles = (long long)((s.K + bm - 1) / bm) * ((NTOT + bn - 1) / bn);
-    const int splits = wgrad_splits(tiles, chunks, bm * bn >= 128 * 128);
-    const int cps = (chunks + splits - 1) / splits, nz = (chunks + cps - 1) / cps;
-    WgRowGeom rg;
-    const bool row = !knobs().wg_generic && wg_row_geom<G>(s, &rg);
-    return snprintf(b, n, "Wg igemm<%s> %s slabs=%d", tile_text(t), row ? "WgALoaderRow+WgBLoaderRow" : "WgALoader+WgBLoader", nz);
+    const Choice c = choose_wgrad<G>(s, kIdeal);
+    if (c.kind == KDirect && c.loader == LFewc)
+        return snprintf(b, n, "Wg direct wgrad_k4s2p1_fewc<mfma16x16x4,C=%d,KT=%d> slabs=%d", s.C, s.K / 16, c.slabs);
+    if (c.kind == KDirect)
+        return snprintf(b, n, "Wg direct %s slabs=%d", c.loader == LFewk ? "wgrad_k3_fewk<fma>" : "wgrad_smallch_k3<mfma16x16x4>",
+                        c.slabs);
+    if (c.kind == KIgemm2w)
+        return snprintf(b, n, "Wg igemm2w<%s> %s<CW=%d>(both operands LDS-DMA) slabs=%d", tile_text(c.tile),
+                        is_k4s2p1<G>() ? "WgImgB2" : "WgImgBG", c.cw, c.slabs);
+    if (c.kind == KIgemm2r)
+        return snprintf(b, n, "Wg igemm2r<%s> WgALoaderRow+WgBLoaderRow(register-staged) slabs=%d", tile_text(c.tile), c.slabs);
+    return snprintf(b, n, "Wg igemm<%s> %s slabs=%d", tile_text(c.tile),
+                    c.loader == LWgRow ? "WgALoaderRow+WgBLoaderRow" : "WgALoader+WgBLoader", c.slabs);
 }
 
 extern "C" {

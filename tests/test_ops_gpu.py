@@ -1623,3 +1623,107 @@ def test_small_channel_transposed_conv_5x5(case):
     ref = torch.tanh(torch.nn.grad.conv2d_input((N, C, H, H), w, gy, stride=2, padding=2) + b.view(1, -1, 1, 1))
     out = F._conv_dgrad_raw(gy.cuda(), w.cuda(), b.cuda(), geom, (H, H), F.ACT_TANH, 0.0)
     assert out.shape == ref.shape and rel(out, ref) < TOL
+
+
+def _plan_text(op, N, C, H, K):
+    import ctypes
+    from lightning_gan_zoo_amd._lib import lib
+    buf = ctypes.create_string_buffer(256)
+    assert lib.gz_conv2d_plan(op, N, C, H, H, K, H // 2, H // 2, 4, 4, 2, 1, buf, 256) >= 0
+    return buf.value.decode()
+
+
+def _offset_view(t):
+    """The same values on the GPU, 4 bytes off a 16-byte boundary."""
+    return torch.empty(t.numel() + 1, device="cuda")[1:].view_as(t).copy_(t)
+
+
+# (N, C, H, K): the two shapes of test_conv_with_fused_batchnorm_statistics whose forward plan is igemm2 -- the input
+# gradient of the first is planned on igemm with the row loaders, which have an element-wise fallback of their own --
+# and one more whose input gradient takes the 256x64 igemm2 tile (the second's takes 512x64)
+UNALIGNED_CASES = [(64, 16, 32, 256), (512, 64, 32, 128), (128, 64, 32, 128)]
+
+
+@pytest.mark.parametrize("case", UNALIGNED_CASES)
+def test_conv_unaligned_operand_contract(case):
+    """k4 s2 p1 launches planned on igemm2: an operand 4 bytes off alignment makes the plain entry points fall back to
+    the element-wise loaders (same numbers), and makes the statistics entry point return GZ_ERR_BAD_SHAPE untouched."""
+    F = _F()
+    from lightning_gan_zoo_amd._lib import lib
+    from lightning_gan_zoo_amd.functional._base import _p, _packed, _stream
+    N, C, H, K = case
+    OH = H // 2
+    g = F.K4S2P1
+    assert "F igemm2<" in _plan_text(0, N, C, H, K)
+    assert ("Dg igemm2<" if case != UNALIGNED_CASES[0] else "Dg igemm<128x32> ConvDgALoaderRow4") in _plan_text(1, N, C, H, K)
+    torch.set_num_threads(min(16, torch.get_num_threads()))
+    x, w, gy = rnd(N, C, H, H, seed=51), rnd(K, C, 4, 4, seed=52, scale=0.1), rnd(N, K, OH, OH, seed=53)
+    wd = w.cuda()
+    ref_y = TF.conv2d(x, w, None, 2, 1)
+    ref_dx = TF.conv_transpose2d(gy, w, None, 2, 1)
+    y0 = F._conv_fwd_raw(x.cuda(), wd, None, g, F.ACT_NONE, 0.0)
+    xs = _offset_view(x)
+    assert xs.data_ptr() % 16 == 4
+    y1 = F._conv_fwd_raw(xs, wd, None, g, F.ACT_NONE, 0.0)
+    assert rel(y0, ref_y) < TOL and rel(y1, ref_y) < TOL and rel(y1, y0) < 1e-5
+    dx0 = F._conv_dgrad_raw(gy.cuda(), wd, None, g, (H, H), F.ACT_NONE, 0.0)
+    gys = _offset_view(gy)
+    assert gys.data_ptr() % 16 == 4
+    dx1 = F._conv_dgrad_raw(gys, wd, None, g, (H, H), F.ACT_NONE, 0.0)
+    assert rel(dx0, ref_dx) < TOL and rel(dx1, ref_dx) < TOL and rel(dx1, dx0) < 1e-5
+    # the statistics launch takes no fallback
+    rows = lib.gz_conv2d_fwd_stats_rows(N, C, H, H, K, OH, OH, 4, 4, 2, 1)
+    assert rows > 0
+    y = torch.full((N, K, OH, OH), float("nan"), device="cuda")
+    stats = torch.empty((rows, K, 2), device="cuda")
+    nbytes = lib.gz_conv2d_fwd_workspace_bytes(N, C, H, H, K, OH, OH, 4, 4, 2, 1)
+    ws = torch.empty(max(nbytes // 4, 1), device="cuda")
+    rc = lib.gz_conv2d_fwd_stats_ws(_p(xs), _p(_packed(wd, "f", g)), _p(y), _p(stats), _p(ws), nbytes, N, C, H, H, K, OH, OH,
+                                    4, 4, 2, 1, _stream())
+    torch.cuda.synchronize()
+    assert rc == -1
+    assert bool(torch.isnan(y).all())
+
+
+def test_conv_missing_workspace_contract():
+    """A launch whose plan splits its reduction, called without a workspace: the plain entry points run the unsplit
+    fallback (same result), the statistics entry points return GZ_ERR_WORKSPACE."""
+    F = _F()
+    from lightning_gan_zoo_amd._lib import lib
+    from lightning_gan_zoo_amd.functional._base import _p, _packed, _stream
+    N, C, H, K = 32, 256, 16, 512
+    OH = H // 2
+    g = F.K4S2P1
+    assert "F igemm2<256x64>" in _plan_text(0, N, C, H, K) and "slabs=4" in _plan_text(0, N, C, H, K)
+    assert "Dg igemm2<256x64>" in _plan_text(1, N, C, H, K) and "splits=2" in _plan_text(1, N, C, H, K)
+    torch.set_num_threads(min(16, torch.get_num_threads()))
+    x, w, gy = rnd(N, C, H, H, seed=61), rnd(K, C, 4, 4, seed=62, scale=0.1), rnd(N, K, OH, OH, seed=63)
+    xd, wd, gyd = x.cuda(), w.cuda(), gy.cuda()
+    shape = (N, C, H, H, K, OH, OH, 4, 4, 2, 1)
+    y = torch.empty((N, K, OH, OH), device="cuda")
+    rc = lib.gz_conv2d_fwd(_p(xd), _p(_packed(wd, "f", g)), None, _p(y), None, 0, *shape, F.ACT_NONE, 0.0, _stream())
+    assert rc == 0 and rel(y, TF.conv2d(x, w, None, 2, 1)) < TOL
+    stats = torch.empty((lib.gz_conv2d_fwd_stats_rows(*shape), K, 2), device="cuda")
+    assert lib.gz_conv2d_fwd_stats_ws(_p(xd), _p(_packed(wd, "f", g)), _p(y), _p(stats), None, 0, *shape, _stream()) == -3
+    dx = torch.empty((N, C, H, H), device="cuda")
+    rc = lib.gz_conv2d_dgrad(_p(gyd), _p(_packed(wd, "d", g)), None, _p(dx), None, 0, *shape, F.ACT_NONE, 0.0, _stream())
+    assert rc == 0 and rel(dx, TF.conv_transpose2d(gy, w, None, 2, 1)) < TOL
+    stats = torch.empty((lib.gz_conv2d_dgrad_stats_rows(*shape), C, 2), device="cuda")
+    assert lib.gz_conv2d_dgrad_stats_ws(_p(gyd), _p(_packed(wd, "d", g)), _p(dx), _p(stats), None, 0, *shape, _stream()) == -3
+    torch.cuda.synchronize()
+    # onto <= 4 channels the direct kernel needs no workspace and none is advertised; a launch that declines it (x only
+    # 4-byte aligned, or statistics requested) is planned with a split reduction and must not run it without slabs
+    N, C, H, K = 8, 4, 8, 256
+    OH = H // 2
+    shape = (N, C, H, H, K, OH, OH, 4, 4, 2, 1)
+    assert "Dg direct" in _plan_text(1, N, C, H, K) and lib.gz_conv2d_dgrad_workspace_bytes(*shape) == 0
+    w, gy = rnd(K, C, 4, 4, seed=64, scale=0.1), rnd(N, K, OH, OH, seed=65)
+    wd, gyd = w.cuda(), gy.cuda()
+    ref = TF.conv_transpose2d(gy, w, None, 2, 1)
+    for dx in (torch.empty((N, C, H, H), device="cuda"), _offset_view(torch.empty(N, C, H, H))):
+        rc = lib.gz_conv2d_dgrad(_p(gyd), _p(_packed(wd, "d", g)), None, _p(dx), None, 0, *shape, F.ACT_NONE, 0.0, _stream())
+        assert rc == 0 and rel(dx, ref) < TOL, (rc, dx.data_ptr() % 16)
+    dx = torch.empty((N, C, H, H), device="cuda")
+    stats = torch.empty((lib.gz_conv2d_dgrad_stats_rows(*shape), C, 2), device="cuda")
+    assert lib.gz_conv2d_dgrad_stats_ws(_p(gyd), _p(_packed(wd, "d", g)), _p(dx), _p(stats), None, 0, *shape, _stream()) == -3
+    torch.cuda.synchronize()
