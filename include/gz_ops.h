@@ -190,20 +190,32 @@ long long gz_conv3d_pack_fwd_elems(int K, int C, int KS);
 long long gz_conv3d_pack_dgrad_elems(int K, int C, int KS, int S);
 int gz_conv3d_pack_fwd(const float* w, float* wpack, int K, int C, int KS, hipStream_t stream);
 int gz_conv3d_pack_dgrad(const float* w, float* wpack, int K, int C, int KS, int S, int P, hipStream_t stream);
-/* y = act(conv3d(x, w) + bias): input gradient of nn.ConvTranspose3d */
+/* Each launcher decides its kernel once (skeleton, tile, reduction splits) from the shape and from what the call brings;
+ * the *_workspace_bytes of an op is what the slabs of that decision need, 0 when it does not split.  A workspace that
+ * is NULL or smaller than that:
+ *   gz_conv3d_fwd / _dgrad planned on the igemm2 skeleton   return GZ_ERR_WORKSPACE and launch nothing;
+ *   gz_conv3d_fwd / _dgrad planned on igemm                 run unsplit (same result up to summation order);
+ *   gz_conv3d_wgrad                                         uses floor(ws_bytes / (4 * K * C * KS^3)) splits, unsplit
+ *                                                           below 2 (same result up to summation order).
+ * gz_conv3d_plan says which of these a shape is. */
+/* y = act(conv3d(x, w) + bias): input gradient of nn.ConvTranspose3d.  wpack and y 16-byte aligned. */
 int gz_conv3d_fwd(const float* x, const float* wpack, const float* bias, float* y, float* workspace, size_t ws_bytes,
                   int N, int C, int D, int H, int W, int K, int OD, int OH, int OW, int KS, int S, int P, int act,
                   float slope, hipStream_t stream);
-/* split-K scratch of the two launchers above / below (0 = not split; NULL workspace = run unsplit) */
 size_t gz_conv3d_fwd_workspace_bytes(int N, int C, int K, int OD, int OH, int OW, int KS);
 size_t gz_conv3d_dgrad_workspace_bytes(int N, int C, int K, int OD, int OH, int OW, int KS);
-/* x = act(conv_transpose3d(y, w) + bias): nn.ConvTranspose3d forward */
+/* x = act(conv_transpose3d(y, w) + bias): nn.ConvTranspose3d forward.  wpack 16-byte aligned; D, H, W even. */
 int gz_conv3d_dgrad(const float* y, const float* wpack, const float* bias, float* x, float* workspace,
                     size_t ws_bytes, int N, int C, int D, int H, int W, int K, int OD, int OH, int OW, int KS, int S,
                     int P, int act, float slope, hipStream_t stream);
 size_t gz_conv3d_wgrad_workspace_bytes(int N, int C, int K, int OD, int OH, int OW, int KS);
 int gz_conv3d_wgrad(const float* x, const float* y, float* dw, float* workspace, size_t ws_bytes, int N, int C, int D,
                     int H, int W, int K, int OD, int OH, int OW, int KS, int S, int P, hipStream_t stream);
+/* the launch of op (0 F, 1 Dg, 2 Wg) as text, conventions of gz_conv2d_plan (host only; 16-byte aligned tensors and the
+ * advertised workspace assumed): "<op> <skeleton><<tile>> <loader> splits=<n> slabs=<n>"; splits cut the reduction (of
+ * the longest of Dg's 8 phases), slabs are the workspace slices that gives (summed over Dg's phases) */
+int gz_conv3d_plan(int op, int N, int C, int D, int H, int W, int K, int OD, int OH, int OW, int KS, int S, int P,
+                   char* buf, int buflen);
 
 /* ---- HoloGAN rigid-body resampling (hologan_generator.py:198-321 + the permute/flip/reshape of :130-133) ----
  * vox [N,C,S,S,S]; minv [N,16] row-major inverse transforms; out2d [N, C*S, S, S] with

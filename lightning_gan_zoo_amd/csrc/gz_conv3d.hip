@@ -1,82 +1,21 @@
 // C-ABI entry points for the cubic-kernel 3-D convolution family on the fp32 MFMA implicit-GEMM core:
 // HoloGAN's ConvTranspose3d(k3, s2, p1, output_padding 1) forward (= Dg), its input gradient (= F)
 // and weight gradient (= Wg).  Reference call sites: core/models/hologan_generator.py:29-30,55-58.
-#include "gz_igemm.h"
+//
+// As in gz_conv.hip, one function per op -- choose_fwd3 / choose_dgrad3 / choose_wgrad3 -- decides skeleton, loader,
+// tile and splits once (gz_conv_choice.h): launch_*3 switch on the answer, gz_conv3d_*_workspace_bytes size its slabs,
+// gz_conv3d_plan prints it.
+#include <cstdio>
+#include <type_traits>
+
+#include "gz_conv_choice.h"
 #include "../../include/gz_ops.h"
 
 namespace gz {
 
-using C3_128x128 = TileCfg<2, 2, 2, 2>;
-using C3_128x64 = TileCfg<2, 2, 2, 1>;
-using C3_128x32 = TileCfg<4, 1, 1, 1>;
-using C3_64x64 = TileCfg<2, 2, 1, 1>;
-
 static inline int r4(int v) { return (v + 3) & ~3; }
 
-// split-K of under-filled F / Dg launches: same policy as gz_conv.hip (plan_split)
-static int plan3(int tile, long long M, long long N, int Kdim, int ny) {
-    const bool off = knobs().no_splitk;
-    if (off) return 1;
-    const int bm = tile == 3 ? 64 : 128, bn = tile == 0 ? 128 : (tile == 2 ? 32 : 64);
-    const long long tiles = ((M + bm - 1) / bm) * ((N + bn - 1) / bn) * ny;
-    const int chunks = (Kdim + BK - 1) / BK;
-    if (chunks < 16 || tiles >= 2 * cus()) return 1;
-    long long want = (4 * cus() + tiles - 1) / tiles, cap = chunks / 8;
-    long long sp = want < cap ? want : cap;
-    return sp < 2 ? 1 : (int)sp;
-}
-
-static size_t bytes3(int splits, long long M, long long N, int Kdim, int ny) {
-    return splits > 1 ? (size_t)split_nz(Kdim, splits) * ny * M * N * 4 : 0;
-}
-
-// Split-K of the transposed convolution's 8 phases (1, 2, 2, 2, 4, 4, 4, 8 taps for k3 s2 p1): the chunk count per
-// workgroup is chosen from the TOTAL work so that ~1024 workgroups of equal length come out; a phase gets as many
-// slabs as its own reduction needs (GridMap::phase_nz), not the longest phase's count.
-struct DgPlan3 {
-    int splits;         // of the longest phase
-    long long slabs;    // sum over the phases
-};
-
-static DgPlan3 plan3_dg(int tile, long long Mp, long long C, int K, int KS, int S, int P) {
-    DgPlan3 none{1, 0};
-    const bool off = knobs().no_splitk;
-    const bool even = knobs().dg3_even_split;      // experiment: the round-1 plan (same slab count per phase)
-    const int bm = tile == 3 ? 64 : 128, bn = tile == 0 ? 128 : (tile == 2 ? 32 : 64);
-    const long long tp = ((Mp + bm - 1) / bm) * ((C + bn - 1) / bn);
-    int pc[8], maxpc = 0;
-    long long total = 0;
-    for (int ph = 0; ph < S * S * S; ++ph) {
-        pc[ph] = (K * dg_taps(KS, S, P, ph / (S * S)) * dg_taps(KS, S, P, (ph / S) % S) * dg_taps(KS, S, P, ph % S) +
-                  BK - 1) / BK;
-        total += pc[ph];
-        maxpc = pc[ph] > maxpc ? pc[ph] : maxpc;
-    }
-    if (off || maxpc < 16 || tp * S * S * S >= 2 * cus()) return none;
-    int splits;
-    if (even) {
-        splits = plan3(tile, Mp, C, K * 8, 8);
-    } else {
-        long long cps = (total * tp + 4 * cus() - 1) / (4 * cus());
-        if (cps < 8) cps = 8;
-        splits = (int)((maxpc + cps - 1) / cps);
-    }
-    if (splits < 2) return none;
-    const int cps = (maxpc + splits - 1) / splits;
-    long long slabs = 0;
-    for (int ph = 0; ph < S * S * S; ++ph) slabs += (pc[ph] + cps - 1) / cps;
-    return DgPlan3{splits, slabs};
-}
-
-static int pick3(long long M, long long N, int ny) {
-    if (N <= 32) return 2;
-    auto tiles = [&](int bm, int bn) { return ((M + bm - 1) / bm) * ((N + bn - 1) / bn) * ny; };
-    if (N <= 64) return tiles(128, 64) >= cus() ? 1 : 3;
-    if (tiles(128, 128) >= cus()) return 0;
-    if (tiles(128, 64) >= cus()) return 1;
-    return 3;
-}
-
+// ---- weight images -------------------------------------------------------------------------------------------------
 // wp[col][ld] = w[r][col] (r < R rows of length COLS), zero padded to ld
 __global__ __launch_bounds__(256) void transpose_pad3_kernel(const float* __restrict__ src, float* __restrict__ dst,
                                                              int R, int COLS, int ld) {
@@ -134,6 +73,35 @@ __global__ __launch_bounds__(256) void pack_dgrad3_kernel(const float* __restric
         dst[((long long)K * taps + (long long)ko * pad) * ldc + i] = 0.f;
 }
 
+// Whether the transposed form runs on the igemm2 skeleton with its weight rows tap-major per phase.  THE predicate: the
+// pack size (gz_conv3d_pack_dgrad_elems), the pack kernel (gz_conv3d_pack_dgrad) and the launch (choose_dgrad3) all ask
+// it and nothing else, so the image that was packed is the image that is read.
+// Multiples of 128 columns only: with 64 (HoloGAN's block2, 8-64 chunks per workgroup) the 256x64 tile measured 164 us
+// against 147 us on the round-1 kernel, and a 512x64 tile needs more gather pieces per k-step than the stream holds.
+static bool dg3_tap2(int K, int C) {
+    return !knobs().no_igemm2 && !knobs().no_igemm2_tap && K >= BK && (C & 127) == 0;
+}
+
+// wp[phase][(tap, ko)][ldc] = w[ko][c][kd][ky][kx] over the phase's own nd x ny x nx taps (tap = (td * ny + ty) * nx +
+// tx, k* = ((p* + P) % S) + S * t*), ko padded to a multiple of BK with zero rows; the unused tail of a phase's
+// fixed-size T^3 * kpad-row region is never read
+__global__ __launch_bounds__(256) void pack_dgrad3_tap_kernel(const float* __restrict__ w, float* __restrict__ wp, int K,
+                                                              int C, int KS, int S, int P, int T, int kpad, int ldc) {
+    const int phase = blockIdx.y;
+    const int pd = phase / (S * S), py = (phase / S) % S, px = phase % S;
+    const int rd = (pd + P) % S, ry = (py + P) % S, rx = (px + P) % S;
+    const int nd = dg_taps(KS, S, P, pd), ny = dg_taps(KS, S, P, py), nx = dg_taps(KS, S, P, px);
+    float* dst = wp + (long long)phase * T * T * T * kpad * ldc;
+    const long long total = (long long)nd * ny * nx * kpad * ldc;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+        const int c = (int)(i % ldc);
+        const long long row = i / ldc;
+        const int ko = (int)(row % kpad), tap = (int)(row / kpad);
+        const int kd = rd + S * (tap / (ny * nx)), ky = ry + S * ((tap / nx) % ny), kx = rx + S * (tap % nx);
+        dst[i] = (ko < K && c < C) ? w[((((long long)ko * C + c) * KS + kd) * KS + ky) * KS + kx] : 0.f;
+    }
+}
+
 __global__ __launch_bounds__(256) void reduce_slabs3_kernel(const float* __restrict__ slab, float* __restrict__ out,
                                                             int S, long long count) {
     long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -141,6 +109,16 @@ __global__ __launch_bounds__(256) void reduce_slabs3_kernel(const float* __restr
     float acc = 0.f;
     for (int s = 0; s < S; ++s) acc += slab[(long long)s * count + i];
     out[i] = acc;
+}
+
+__global__ __launch_bounds__(256) void act_inplace3_kernel(float* __restrict__ x, long long total4, int act, float slope) {
+    const long long stride = (long long)gridDim.x * 256;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total4; i += stride) {
+        f32x4 v = reinterpret_cast<f32x4*>(x)[i];
+        v[0] = act_fwd(v[0], act, slope); v[1] = act_fwd(v[1], act, slope);
+        v[2] = act_fwd(v[2], act, slope); v[3] = act_fwd(v[3], act, slope);
+        reinterpret_cast<f32x4*>(x)[i] = v;
+    }
 }
 
 static bool shape3_ok(const Conv3DShape& s, int KS, int S, int P) {
@@ -151,16 +129,43 @@ static bool shape3_ok(const Conv3DShape& s, int KS, int S, int P) {
 
 static bool big3(long long e) { return e * 4 >= (1ll << 31); }
 
+// ---- the launches --------------------------------------------------------------------------------------------------
+// Reduction chunks per phase of the transposed form (1, 2, 2, 2, 4, 4, 4, 8 taps for k3 s2 p1), counted here and nowhere
+// else: choose_dgrad3 sizes splits and slabs from them, run_dgrad3 / run_dgradtap3 hand them to the launcher.
+struct Phases3 {
+    int n, pc[8], maxpc;
+    long long total;
+    // slabs when the longest phase is cut into `splits` pieces: a phase gets as many as its own reduction needs
+    // (GridMap::phase_nz), not the longest phase's count
+    int slabs(int splits) const {
+        const int per = (maxpc + splits - 1) / splits;
+        int sum = 0;
+        for (int ph = 0; ph < n; ++ph) sum += (pc[ph] + per - 1) / per;
+        return sum;
+    }
+};
+
+static Phases3 dg3_phases(int K, int KS, int S, int P, bool tap2) {      // tap2: whole BK-blocks of K per tap (dg3_tap2)
+    Phases3 p{S * S * S, {}, 0, 0};
+    for (int ph = 0; ph < p.n; ++ph) {
+        const int taps = dg_taps(KS, S, P, ph / (S * S)) * dg_taps(KS, S, P, (ph / S) % S) * dg_taps(KS, S, P, ph % S);
+        p.pc[ph] = tap2 ? taps * (round_bk(K) / BK) : (K * taps + BK - 1) / BK;
+        p.total += p.pc[ph];
+        p.maxpc = p.pc[ph] > p.maxpc ? p.pc[ph] : p.maxpc;
+    }
+    return p;
+}
+
 template <class Cfg, int KS, int S, int P>
 static int run_fwd3(const float* x, const float* wp, const float* bias, float* y, const Conv3DShape& s, int act,
-                    float slope, hipStream_t st, int splits, float* slab) {
+                    float slope, hipStream_t st, Loader ld, int splits, float* slab) {
     using AL = Conv3DFwdALoader<Cfg::BM, KS, S, P>;
     using BL = MContigLoader4<Cfg::BN>;
     const int osp = s.OD * s.OH * s.OW;
     typename AL::Params pa{x, s, make_fastdiv(osp), make_fastdiv(s.OH * s.OW), make_fastdiv(s.OW)};
     int M = s.N * osp;
     EpiNCHW::Params pe{y, M, s.K, osp, make_fastdiv(osp), bias, act, slope};
-    if (fwd3_tap_major(s.C)) {
+    if (ld == LTap) {
         using ALT = Conv3DFwdALoaderTap<Cfg::BM, KS, S, P>;
         int Kt = KS * KS * KS * round_bk(s.C);
         typename BL::Params pbt{wp, Kt, r4(s.K), r4(s.K), 0};
@@ -185,204 +190,40 @@ static int run_dgrad3(const float* y, const float* wp, const float* bias, float*
     int M = s.N * AD * AH * AW;
     typename Epi::Params pe{x, M, s.C, s.D, s.H, s.W, AD, AH, AW, make_fastdiv(AD * AH * AW), make_fastdiv(AH * AW),
                             make_fastdiv(AW), bias, act, slope};
-    int pc[8];
-    for (int ph = 0; ph < S * S * S; ++ph)
-        pc[ph] = (s.K * dg_taps(KS, S, P, ph / (S * S)) * dg_taps(KS, S, P, (ph / S) % S) * dg_taps(KS, S, P, ph % S) +
-                  BK - 1) / BK;
-    return launch_igemm<Cfg, AL, BL, Epi>(pa, pb, pe, M, s.C, Kg, S * S * S, splits, st, slab, pc);
+    const Phases3 ph = dg3_phases(s.K, KS, S, P, false);
+    return launch_igemm<Cfg, AL, BL, Epi>(pa, pb, pe, M, s.C, Kg, S * S * S, splits, st, slab, ph.pc);
 }
 
-static int splits3(long long tiles, int chunks) {
-    const int target = knobs().wg3_target * cus() / 256;
-    if (tiles >= cus()) return 1;
-    long long want = (target + tiles - 1) / tiles;
-    long long cap = chunks / 8 > 0 ? chunks / 8 : 1;
-    long long s = want < cap ? want : cap;
-    return (int)(s < 1 ? 1 : s);
-}
-
-template <class Cfg, int KS, int S, int P>
-static int run_wgrad3(const float* x, const float* y, float* dw, float* ws, size_t ws_bytes, const Conv3DShape& s,
+// Weight gradient on either skeleton (KD = KIgemm: igemm_kernel; KIgemm2r: igemm2r_kernel with the same register-staged
+// loaders): a split launch writes c.slabs slabs of K x C*KS^3 floats to the workspace, reduce_slabs3_kernel sums them
+// in slab order.
+template <class Cfg, Kind KD, int KS, int S, int P>
+static int run_wgrad3(const float* x, const float* y, float* dw, float* ws, const Conv3DShape& s, const Choice& c,
                       hipStream_t st) {
     using AL = WgALoader<Cfg::BM>;
     using BL = Wg3DBLoader<Cfg::BN, KS, S, P>;
+    using Epi = std::conditional_t<KD == KIgemm2r, EpiRowMajorB, EpiRowMajor>;
     const int osp = s.OD * s.OH * s.OW;
     const int KTOT = s.N * osp;
     const int NTOT = s.C * KS * KS * KS;
     ConvShape flat{s.N, s.C, 1, 1, s.K, osp, 1};      // WgALoader only needs N, K and OH*OW
     typename AL::Params pa{y, flat, make_fastdiv(osp), KTOT};
     typename BL::Params pb{x, s, make_fastdiv(osp), make_fastdiv(s.OH * s.OW), make_fastdiv(s.OW), KTOT, NTOT};
-    long long tiles = (long long)((s.K + Cfg::BM - 1) / Cfg::BM) * ((NTOT + Cfg::BN - 1) / Cfg::BN);
-    int chunks = (KTOT + BK - 1) / BK;
-    int splits = splits3(tiles, chunks);
-    long long count = (long long)s.K * NTOT;
-    if (splits > 1) {
-        long long max_splits = (long long)(ws_bytes / 4) / count;
-        if (max_splits < 2) splits = 1;
-        else if (splits > max_splits) splits = (int)max_splits;
-    }
-    int cps = (chunks + splits - 1) / splits;
-    int nz = (chunks + cps - 1) / cps;
-    float* out = nz > 1 ? ws : dw;
-    EpiRowMajor::Params pe{out, s.K, NTOT, NTOT, count, nullptr, ACT_NONE, 0.f};
-    int rc = launch_igemm<Cfg, AL, BL, EpiRowMajor>(pa, pb, pe, s.K, NTOT, KTOT, 1, splits, st);
-    if (rc != GZ_OK) return rc;
-    if (nz > 1) {
-        hipLaunchKernelGGL(reduce_slabs3_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, st, ws, dw, nz,
-                           count);
-        rc = launch_status();
-    }
-    return rc;
+    const long long count = (long long)s.K * NTOT;
+    typename Epi::Params pe{c.slabs > 1 ? ws : dw, s.K, NTOT, NTOT, count, nullptr, ACT_NONE, 0.f};
+    int rc;
+    if constexpr (KD == KIgemm2r) rc = launch_igemm2r<Cfg, AL, BL, Epi>(pa, pb, pe, s.K, NTOT, KTOT, c.splits, st);
+    else rc = launch_igemm<Cfg, AL, BL, Epi>(pa, pb, pe, s.K, NTOT, KTOT, 1, c.splits, st);
+    if (rc != GZ_OK || c.slabs <= 1) return rc;
+    hipLaunchKernelGGL(reduce_slabs3_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, st, ws, dw, c.slabs,
+                       count);
+    return launch_status();
 }
 
 // ---- the igemm2 skeleton for the two gather-fed directions (round 4) -----------------------------------------
 // The round-1 kernels above run HoloGAN's two ConvTranspose3d layers at 89-100 TFLOP/s forward and 95-104 on the input
 // gradient; the one-wavefront-per-SIMD skeleton with 4-byte LDS-DMA gathers (Conv3DDgTapA2 / Conv3DTapA2) takes them
-// when the GEMM's column count is a multiple of 64.  tile: 0 = not taken, 1 = 256x128, 2 = 256x64.
-using C3_256x128 = TileCfg2<2, 2, 2, 2>;
-using C3_256x64 = TileCfg2<2, 2, 1, 3>;
-
-struct Plan3T {
-    int tile, splits;
-    long long slabs;      // split launches of the transposed form: slabs summed over the phases
-};
-
-// transposed form: weight rows tap-major per phase (pack_dgrad3_tap_kernel) -- the pack and the launch must agree.
-// Multiples of 128 columns only: with 64 (HoloGAN's block2, 8-64 chunks per workgroup) the 256x64 tile measured 164 us
-// against 147 us on the round-1 kernel, and a 512x64 tile needs more gather pieces per k-step than the stream holds.
-static bool dg3_tap2(int K, int C) {
-    return !knobs().no_igemm2 && !knobs().no_igemm2_tap && K >= BK && (C & 127) == 0;
-}
-
-static Plan3T plan3_dgtap2(long long Mp, int C, int K, int KS, int S, int P) {
-    if (!dg3_tap2(K, C) || S * S * S > 8) return Plan3T{0, 1, 0};
-    const int kblocks = round_bk(K) / BK;
-    int pc[8], maxpc = 0;
-    long long total = 0;
-    for (int ph = 0; ph < S * S * S; ++ph) {
-        pc[ph] = dg_taps(KS, S, P, ph / (S * S)) * dg_taps(KS, S, P, (ph / S) % S) * dg_taps(KS, S, P, ph % S) * kblocks;
-        total += pc[ph];
-        maxpc = pc[ph] > maxpc ? pc[ph] : maxpc;
-    }
-    const long long tm = (Mp + 255) / 256;
-    // 256x128 also when its tiles alone do not fill the chip (HoloGAN block1 at bs 64, 128 tiles, 27 slabs: 184 us
-    // against 193 us on 256x64 tiles with 21 slabs; the round-1 kernel: 223 us)
-    const int tile = knobs().dg3_tile == 2 ? 2 : 1;
-    const long long tp = tm * (tile == 1 ? C / 128 : C / 64);
-    // phases of 1..8 taps: with >= 4 workgroups per CU the longest-first launch order balances them; below that the
-    // reduction is cut into pieces of equal length (>= 32 chunks), ~2 workgroups per CU
-    if (knobs().no_splitk || tp * S * S * S >= 4LL * cus()) return Plan3T{tile, 1, 0};
-    const int wgs = knobs().dg3_wgs * cus();
-    long long cps = (total * tp + wgs - 1) / wgs;
-    if (cps < knobs().dg3_min_chunks) cps = knobs().dg3_min_chunks;
-    const int splits = (int)((maxpc + cps - 1) / cps);
-    if (splits < 2) return Plan3T{tile, 1, 0};
-    const int per = (maxpc + splits - 1) / splits;
-    long long slabs = 0;
-    for (int ph = 0; ph < S * S * S; ++ph) slabs += (pc[ph] + per - 1) / per;
-    return Plan3T{tile, splits, slabs};
-}
-
-// plain strided form (the transposed layer's input gradient): the tap-major forward image is the one already packed
-static Plan3T plan3_fwdtap2(long long M, int K, int C, int KS) {
-    if (knobs().no_igemm2 || knobs().no_igemm2_tap || !fwd3_tap_major(C) || (K & 63)) return Plan3T{0, 1, 0};
-    const int chunks = KS * KS * KS * round_bk(C) / BK;
-    const long long tm = (M + 255) / 256, t64 = tm * (K / 64), t128 = (K & 127) ? 0 : tm * (K / 128);
-    const int cu = cus();
-    if (t128 >= cu * 7 / 8) return Plan3T{1, 1, 0};
-    if (t64 >= cu * 7 / 8) return Plan3T{2, 1, 0};
-    if (knobs().no_splitk) return Plan3T{0, 1, 0};
-    for (int tile = t128 ? 1 : 2; tile <= 2; ++tile) {
-        const long long tiles = tile == 1 ? t128 : t64;
-        int splits = (int)((cu + tiles - 1) / tiles);
-        while (splits > 1 && chunks / splits < 48) --splits;
-        if (splits > 1 && tiles * splits >= cu * 3 / 4) return Plan3T{tile, splits, 0};
-    }
-    return Plan3T{0, 1, 0};
-}
-
-// wp[phase][(tap, ko)][ldc] = w[ko][c][kd][ky][kx] over the phase's own nd x ny x nx taps (tap = (td * ny + ty) * nx +
-// tx, k* = ((p* + P) % S) + S * t*), ko padded to a multiple of BK with zero rows; the unused tail of a phase's
-// fixed-size T^3 * kpad-row region is never read
-__global__ __launch_bounds__(256) void pack_dgrad3_tap_kernel(const float* __restrict__ w, float* __restrict__ wp, int K,
-                                                              int C, int KS, int S, int P, int T, int kpad, int ldc) {
-    const int phase = blockIdx.y;
-    const int pd = phase / (S * S), py = (phase / S) % S, px = phase % S;
-    const int rd = (pd + P) % S, ry = (py + P) % S, rx = (px + P) % S;
-    const int nd = dg_taps(KS, S, P, pd), ny = dg_taps(KS, S, P, py), nx = dg_taps(KS, S, P, px);
-    float* dst = wp + (long long)phase * T * T * T * kpad * ldc;
-    const long long total = (long long)nd * ny * nx * kpad * ldc;
-    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
-        const int c = (int)(i % ldc);
-        const long long row = i / ldc;
-        const int ko = (int)(row % kpad), tap = (int)(row / kpad);
-        const int kd = rd + S * (tap / (ny * nx)), ky = ry + S * ((tap / nx) % ny), kx = rx + S * (tap % nx);
-        dst[i] = (ko < K && c < C) ? w[((((long long)ko * C + c) * KS + kd) * KS + ky) * KS + kx] : 0.f;
-    }
-}
-
-__global__ __launch_bounds__(256) void act_inplace3_kernel(float* __restrict__ x, long long total4, int act, float slope) {
-    const long long stride = (long long)gridDim.x * 256;
-    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total4; i += stride) {
-        f32x4 v = reinterpret_cast<f32x4*>(x)[i];
-        v[0] = act_fwd(v[0], act, slope); v[1] = act_fwd(v[1], act, slope);
-        v[2] = act_fwd(v[2], act, slope); v[3] = act_fwd(v[3], act, slope);
-        reinterpret_cast<f32x4*>(x)[i] = v;
-    }
-}
-
-// weight gradient on the igemm2 skeleton with the register-staged loaders above (igemm2r_kernel, as the 2-D layers
-// without an LDS-DMA image).  Split so that two workgroups per CU come out, >= 24 chunks each: HoloGAN block1 (54 tiles
-// x 9 splits) 238 -> 178 us, block2 (7 tiles x 73) 210 -> 205 us; pieces of 48-64 chunks leave a partial second round
-// of workgroups and measured 240-310 us.
-// (256 x 128 tiles, or 128 x 256 with fewer than 256 output channels)
-using C3_128x256 = TileCfg2<1, 4, 2, 2>;
-static bool wg3r_ok(const Conv3DShape& s) { return !knobs().no_igemm2 && !knobs().no_wg3r && s.K >= 128; }
-
-static int wg3r_splits(const Conv3DShape& s, int KS) {
-    const long long ntot = (long long)s.C * KS * KS * KS;
-    const long long tiles = s.K >= 256 ? (long long)((s.K + 255) / 256) * ((ntot + 127) / 128)
-                                       : (long long)((s.K + 127) / 128) * ((ntot + 255) / 256);
-    const int chunks = (s.N * s.OD * s.OH * s.OW + BK - 1) / BK;
-    int splits = (int)(knobs().wg3r_wgs * cus() / tiles);
-    if (splits < 1) splits = 1;
-    while (splits > 1 && chunks / splits < knobs().wg3r_min_chunks) --splits;
-    return splits;
-}
-
-template <class Cfg, int KS, int S, int P>
-static int run_wgrad3r(const float* x, const float* y, float* dw, float* ws, size_t ws_bytes, const Conv3DShape& s,
-                       hipStream_t st) {
-    using AL = WgALoader<Cfg::BM>;
-    using BL = Wg3DBLoader<Cfg::BN, KS, S, P>;
-    const int osp = s.OD * s.OH * s.OW;
-    const int KTOT = s.N * osp;
-    const int NTOT = s.C * KS * KS * KS;
-    ConvShape flat{s.N, s.C, 1, 1, s.K, osp, 1};
-    typename AL::Params pa{y, flat, make_fastdiv(osp), KTOT};
-    typename BL::Params pb{x, s, make_fastdiv(osp), make_fastdiv(s.OH * s.OW), make_fastdiv(s.OW), KTOT, NTOT};
-    const int chunks = (KTOT + BK - 1) / BK;
-    int splits = wg3r_splits(s, KS);
-    const long long count = (long long)s.K * NTOT;
-    if (splits > 1) {
-        const long long max_splits = (long long)(ws_bytes / 4) / count;
-        if (max_splits < 2) splits = 1;
-        else if (splits > max_splits) splits = (int)max_splits;
-    }
-    const int cps = (chunks + splits - 1) / splits;
-    const int nz = (chunks + cps - 1) / cps;
-    float* out = nz > 1 ? ws : dw;
-    EpiRowMajorB::Params pe{out, s.K, NTOT, NTOT, count, nullptr, ACT_NONE, 0.f};
-    int rc = launch_igemm2r<Cfg, AL, BL, EpiRowMajorB>(pa, pb, pe, s.K, NTOT, KTOT, splits, st);
-    if (rc != GZ_OK) return rc;
-    if (nz > 1) {
-        hipLaunchKernelGGL(reduce_slabs3_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, st, ws, dw, nz,
-                           count);
-        rc = launch_status();
-    }
-    return rc;
-}
-
+// when the GEMM's column count is a multiple of 64 (256x128 or 256x64 tiles).
 template <class Cfg, int KS, int S, int P>
 static int run_dgradtap3(const float* y, const float* wp, const float* bias, float* x, const Conv3DShape& s, int act,
                          float slope, hipStream_t st, int splits, float* slab) {
@@ -396,10 +237,8 @@ static int run_dgradtap3(const float* y, const float* wp, const float* bias, flo
     const int M = s.N * AD * AH * AW;
     typename Epi::Params pe{x, M, s.C, s.D, s.H, s.W, AD, AH, AW, make_fastdiv(AD * AH * AW), make_fastdiv(AH * AW),
                             make_fastdiv(AW), bias, act, slope};
-    int pc[8];
-    for (int ph = 0; ph < S * S * S; ++ph)
-        pc[ph] = dg_taps(KS, S, P, ph / (S * S)) * dg_taps(KS, S, P, (ph / S) % S) * dg_taps(KS, S, P, ph % S) * (kpad / BK);
-    const int rc = launch_igemm2<Cfg, AL, BL, Epi>(pa, pb, pe, M, s.C, Kt, S * S * S, splits, st, slab, pc);
+    const Phases3 ph = dg3_phases(s.K, KS, S, P, true);
+    const int rc = launch_igemm2<Cfg, AL, BL, Epi>(pa, pb, pe, M, s.C, Kt, S * S * S, splits, st, slab, ph.pc);
     if (rc != GZ_OK || act == ACT_NONE) return rc;
     // (EpiPhase3DB adds the bias only; no shipped model puts an activation on a ConvTranspose3d)
     const long long total4 = (long long)s.N * s.C * s.D * s.H * s.W / 4;       // D, H, W even: a multiple of 8 elements
@@ -421,17 +260,206 @@ static int run_fwdtap3(const float* x, const float* wp, const float* bias, float
     return launch_igemm2<Cfg, AL, BL, EpiNCHWB>(pa, pb, pe, M, s.K, Kt, 1, splits, st, slab);
 }
 
+// ---- the launch choice of each op, and the one function that executes it -------------------------------------------
+// The choosers read C and the feature side of the shape only (N, K, OD, OH, OW): all that a workspace query knows.
+static long long tiles3(TileId t, long long M, long long N, int ny) {
+    const int bm = t == T64x64 ? 64 : 128, bn = t == T128x128 ? 128 : (t == T128x32 ? 32 : 64);
+    return ((M + bm - 1) / bm) * ((N + bn - 1) / bn) * ny;
+}
+
+static TileId pick3(long long M, long long N, int ny) {
+    if (N <= 32) return T128x32;
+    if (N <= 64) return tiles3(T128x64, M, N, ny) >= cus() ? T128x64 : T64x64;
+    if (tiles3(T128x128, M, N, ny) >= cus()) return T128x128;
+    if (tiles3(T128x64, M, N, ny) >= cus()) return T128x64;
+    return T64x64;
+}
+
+// split-K of under-filled F / Dg launches: same policy as gz_conv.hip (plan_split)
+static int plan3(TileId tile, long long M, long long N, int Kdim, int ny) {
+    const long long tiles = tiles3(tile, M, N, ny);
+    const int chunks = (Kdim + BK - 1) / BK;
+    if (knobs().no_splitk || chunks < 16 || tiles >= 2 * cus()) return 1;
+    long long want = (4 * cus() + tiles - 1) / tiles, cap = chunks / 8;
+    long long sp = want < cap ? want : cap;
+    return sp < 2 ? 1 : (int)sp;
+}
+
+static size_t slab_bytes(const Choice& c, long long M, long long N) {
+    return c.splits > 1 ? (size_t)c.slabs * M * N * 4 : 0;
+}
+
+// F on igemm2: the tap-major forward image is the one already packed.  KUnsupported: the launch stays on igemm_kernel.
+static Choice fwd3_igemm2(long long M, int K, int C, int KS) {
+    const Choice none = choice_of(KUnsupported, LGeneric, T64x64);
+    if (knobs().no_igemm2 || knobs().no_igemm2_tap || !fwd3_tap_major(C) || (K & 63)) return none;
+    const int chunks = KS * KS * KS * round_bk(C) / BK;
+    const long long tm = (M + 255) / 256, t64 = tm * (K / 64), t128 = (K & 127) ? 0 : tm * (K / 128);
+    const int cu = cus();
+    Choice c = choice_of(KIgemm2, LGather2, t128 >= cu * 7 / 8 ? T256x128 : T256x64);
+    if (t128 >= cu * 7 / 8 || t64 >= cu * 7 / 8) return c;
+    if (knobs().no_splitk) return none;
+    for (int tile = t128 ? 1 : 2; tile <= 2; ++tile) {
+        const long long tiles = tile == 1 ? t128 : t64;
+        c.tile = tile == 1 ? T256x128 : T256x64;
+        c.splits = (int)((cu + tiles - 1) / tiles);
+        while (c.splits > 1 && chunks / c.splits < 48) --c.splits;
+        if (c.splits > 1 && tiles * c.splits >= cu * 3 / 4) return c;
+    }
+    return none;
+}
+
+// Short workspace: an igemm2 launch is refused (GZ_ERR_WORKSPACE, launch_fwd3), an igemm launch runs unsplit.
+static Choice choose_fwd3(const Conv3DShape& s, int KS, const Facts& f) {
+    const long long M = (long long)s.N * s.OD * s.OH * s.OW;
+    const bool tap = fwd3_tap_major(s.C);
+    const int kdim = (tap ? round_bk(s.C) : s.C) * KS * KS * KS;
+    Choice c = fwd3_igemm2(M, s.K, s.C, KS);
+    if (c.kind != KIgemm2 || !f.in4) {
+        c = choice_of(KIgemm, tap ? LTap : LGeneric, pick3(M, s.K, 1));
+        c.splits = plan3(c.tile, M, s.K, kdim, 1);
+    }
+    c.slabs = split_nz(kdim, c.splits);
+    c.ws_short = c.splits > 1 && ws_lacks(f, slab_bytes(c, M, s.K));
+    if (c.ws_short && c.kind == KIgemm) c.splits = c.slabs = 1;
+    return c;
+}
+
+template <int KS, int S, int P>
+static int launch_fwd3(const Choice& c, const float* x, const float* wp, const float* bias, float* y,
+                       const Conv3DShape& s, int act, float slope, float* ws, hipStream_t st) {
+    if (c.kind == KIgemm2 && c.ws_short) return GZ_ERR_WORKSPACE;
+    float* slab = c.splits > 1 ? ws : nullptr;
+    switch (c.tile) {
+        case T256x128: return run_fwdtap3<Cfg256x128, KS, S, P>(x, wp, bias, y, s, act, slope, st, c.splits, slab);
+        case T256x64: return run_fwdtap3<Cfg256x64, KS, S, P>(x, wp, bias, y, s, act, slope, st, c.splits, slab);
+        case T128x128: return run_fwd3<Cfg128x128, KS, S, P>(x, wp, bias, y, s, act, slope, st, c.loader, c.splits, slab);
+        case T128x64: return run_fwd3<Cfg128x64, KS, S, P>(x, wp, bias, y, s, act, slope, st, c.loader, c.splits, slab);
+        case T128x32: return run_fwd3<Cfg128x32, KS, S, P>(x, wp, bias, y, s, act, slope, st, c.loader, c.splits, slab);
+        default: return run_fwd3<Cfg64x64, KS, S, P>(x, wp, bias, y, s, act, slope, st, c.loader, c.splits, slab);
+    }
+}
+
+// Split-K of the transposed convolution's 8 phases: the chunk count per workgroup is chosen from the TOTAL work so that
+// workgroups of equal length come out (~1024 on igemm; ~2 per CU of >= 32 chunks on igemm2); c.splits cuts the longest
+// phase, c.slabs sums Phases3::slabs.  Short workspace: as for F (the packed image is tap-major or not -- dg3_tap2 --
+// so an igemm2 launch has no other kernel to fall back to).
+static Choice choose_dgrad3(const Conv3DShape& s, int KS, int S, int P, const Facts& f) {
+    const long long Mp = (long long)s.N * s.OD * s.OH * s.OW;      // rows per phase: D = S * OD
+    const int ny = S * S * S;
+    const bool tap2 = dg3_tap2(s.K, s.C);
+    const Phases3 ph = dg3_phases(s.K, KS, S, P, tap2);
+    Choice c = choice_of(tap2 ? KIgemm2 : KIgemm, tap2 ? LGather2 : LGeneric, T64x64);
+    if (tap2) {
+        // 256x128 also when its tiles alone do not fill the chip (HoloGAN block1 at bs 64, 128 tiles, 27 slabs: 184 us
+        // against 193 us on 256x64 tiles with 21 slabs; the round-1 kernel: 223 us)
+        c.tile = knobs().dg3_tile == 2 ? T256x64 : T256x128;
+        const long long tp = ((Mp + 255) / 256) * (c.tile == T256x128 ? s.C / 128 : s.C / 64);
+        // phases of 1..8 taps: with >= 4 workgroups per CU the longest-first launch order balances them; below that the
+        // reduction is cut into pieces of equal length (>= 32 chunks), ~2 workgroups per CU
+        if (!knobs().no_splitk && tp * ny < 4LL * cus()) {
+            const int wgs = knobs().dg3_wgs * cus();
+            long long cps = (ph.total * tp + wgs - 1) / wgs;
+            if (cps < knobs().dg3_min_chunks) cps = knobs().dg3_min_chunks;
+            c.splits = (int)((ph.maxpc + cps - 1) / cps);
+        }
+    } else {
+        c.tile = pick3(Mp, s.C, ny);
+        const long long tp = tiles3(c.tile, Mp, s.C, 1);
+        if (!knobs().no_splitk && ph.maxpc >= 16 && tp * ny < 2 * cus()) {
+            long long cps = (ph.total * tp + 4 * cus() - 1) / (4 * cus());
+            if (cps < 8) cps = 8;
+            // (GZ_DG3_EVEN_SPLIT: the round-1 plan, sized as if every phase had 8 taps)
+            c.splits = knobs().dg3_even_split ? plan3(c.tile, Mp, s.C, s.K * 8, 8) : (int)((ph.maxpc + cps - 1) / cps);
+        }
+    }
+    if (c.splits < 2) c.splits = 1;
+    else c.slabs = ph.slabs(c.splits);
+    c.ws_short = c.splits > 1 && ws_lacks(f, slab_bytes(c, Mp, s.C));
+    if (c.ws_short && c.kind == KIgemm) c.splits = c.slabs = 1;
+    return c;
+}
+
+template <int KS, int S, int P>
+static int launch_dgrad3(const Choice& c, const float* y, const float* wp, const float* bias, float* x,
+                         const Conv3DShape& s, int act, float slope, float* ws, hipStream_t st) {
+    if (c.kind == KIgemm2 && c.ws_short) return GZ_ERR_WORKSPACE;
+    float* slab = c.splits > 1 ? ws : nullptr;
+    switch (c.tile) {
+        case T256x128: return run_dgradtap3<Cfg256x128, KS, S, P>(y, wp, bias, x, s, act, slope, st, c.splits, slab);
+        case T256x64: return run_dgradtap3<Cfg256x64, KS, S, P>(y, wp, bias, x, s, act, slope, st, c.splits, slab);
+        case T128x128: return run_dgrad3<Cfg128x128, KS, S, P>(y, wp, bias, x, s, act, slope, st, c.splits, slab);
+        case T128x64: return run_dgrad3<Cfg128x64, KS, S, P>(y, wp, bias, x, s, act, slope, st, c.splits, slab);
+        case T128x32: return run_dgrad3<Cfg128x32, KS, S, P>(y, wp, bias, x, s, act, slope, st, c.splits, slab);
+        default: return run_dgrad3<Cfg64x64, KS, S, P>(y, wp, bias, x, s, act, slope, st, c.splits, slab);
+    }
+}
+
+// Weight gradient.  K >= 128: the igemm2 skeleton (256 x 128 tiles, or 128 x 256 with fewer than 256 output channels),
+// split so that two workgroups per CU come out, >= 24 chunks each: HoloGAN block1 (54 tiles x 9 splits) 238 -> 178 us,
+// block2 (7 tiles x 73) 210 -> 205 us; pieces of 48-64 chunks leave a partial second round of workgroups and measured
+// 240-310 us.  Short workspace: the splits are clamped to the slabs it holds (wg_fit_splits), unsplit below 2.
+static Choice choose_wgrad3(const Conv3DShape& s, int KS, const Facts& f) {
+    const long long NTOT = (long long)s.C * KS * KS * KS;
+    const int KTOT = s.N * s.OD * s.OH * s.OW, chunks = (KTOT + BK - 1) / BK;
+    Choice c = choice_of(KIgemm, LGeneric, T64x64);
+    if (!knobs().no_igemm2 && !knobs().no_wg3r && s.K >= 128) {
+        c.kind = KIgemm2r;
+        c.tile = s.K >= 256 ? T256x128 : T128x256;
+        const long long tiles = s.K >= 256 ? (long long)((s.K + 255) / 256) * ((NTOT + 127) / 128)
+                                           : (long long)((s.K + 127) / 128) * ((NTOT + 255) / 256);
+        c.splits = (int)(knobs().wg3r_wgs * cus() / tiles);
+        if (c.splits < 1) c.splits = 1;
+        while (c.splits > 1 && chunks / c.splits < knobs().wg3r_min_chunks) --c.splits;
+    } else {
+        c.tile = NTOT <= 32 ? T128x32 : ((NTOT <= 64 || s.K <= 64) ? (s.K <= 64 ? T64x64 : T128x64) : T128x128);
+        const int force = knobs().wg3_tile;      // experiment
+        if (force >= 0 && c.tile == T128x128) c.tile = force <= T64x64 ? (TileId)force : T64x64;
+        const long long tiles = tiles3(c.tile, s.K, NTOT, 1);
+        const long long want = (knobs().wg3_target * cus() / 256 + tiles - 1) / tiles, cap = chunks / 8;
+        c.splits = tiles >= cus() ? 1 : (int)(want < cap ? want : cap);
+        if (c.splits < 1) c.splits = 1;
+    }
+    const int wish = c.splits;
+    c.splits = wg_fit_splits(wish, f.ws_bytes, s.K * NTOT);
+    c.ws_short = c.splits < wish;
+    c.slabs = split_nz(KTOT, c.splits);
+    return c;
+}
+
+template <int KS, int S, int P>
+static int launch_wgrad3(const Choice& c, const float* x, const float* y, float* dw, float* ws, const Conv3DShape& s,
+                         hipStream_t st) {
+    switch (c.tile) {
+        case T256x128: return run_wgrad3<Cfg256x128, KIgemm2r, KS, S, P>(x, y, dw, ws, s, c, st);
+        case T128x256: return run_wgrad3<Cfg128x256, KIgemm2r, KS, S, P>(x, y, dw, ws, s, c, st);
+        case T128x128: return run_wgrad3<Cfg128x128, KIgemm, KS, S, P>(x, y, dw, ws, s, c, st);
+        case T128x64: return run_wgrad3<Cfg128x64, KIgemm, KS, S, P>(x, y, dw, ws, s, c, st);
+        case T128x32: return run_wgrad3<Cfg128x32, KIgemm, KS, S, P>(x, y, dw, ws, s, c, st);
+        default: return run_wgrad3<Cfg64x64, KIgemm, KS, S, P>(x, y, dw, ws, s, c, st);
+    }
+}
+
+// The workspace sizes are asked by the feature side alone; the one geometry that exists (k3 s2 p1 between even image
+// sides) has D = 2 * OD, and no chooser reads the image side.
+constexpr int kS3 = 2, kP3 = 1;
+static Conv3DShape shape3_of_features(int N, int C, int K, int OD, int OH, int OW) {
+    return Conv3DShape{N, C, kS3 * OD, kS3 * OH, kS3 * OW, K, OD, OH, OW};
+}
+
+// the A-operand loader a choice of op (0 F, 1 Dg, 2 Wg) runs with, as gz_conv3d_plan names it
+static const char* loader_text3(int op, const Choice& c) {
+    if (op == 2) return c.kind == KIgemm2r ? "WgALoader+Wg3DBLoader(register-staged)" : "WgALoader+Wg3DBLoader";
+    switch (c.loader) {
+        case LGather2: return op == 0 ? "Conv3DTapA2(gather, LDS-DMA 4B)" : "Conv3DDgTapA2(gather, LDS-DMA 4B)";
+        case LTap: return "Conv3DFwdALoaderTap";
+        default: return op == 0 ? "Conv3DFwdALoader" : "Conv3DDgALoader";
+    }
+}
+
 }  // namespace gz
 
 using namespace gz;
-
-#define GZ3_TILE_SWITCH(T, CALL)              \
-    switch (T) {                              \
-        case 0: return CALL(C3_128x128);      \
-        case 1: return CALL(C3_128x64);       \
-        case 2: return CALL(C3_128x32);       \
-        default: return CALL(C3_64x64);       \
-    }
 
 extern "C" {
 
@@ -475,19 +503,18 @@ int gz_conv3d_pack_dgrad(const float* w, float* wp, int K, int C, int KS, int S,
 }
 
 size_t gz_conv3d_fwd_workspace_bytes(int N, int C, int K, int OD, int OH, int OW, int KS) {
-    long long M = (long long)N * OD * OH * OW;
-    int Kg = (fwd3_tap_major(C) ? round_bk(C) : C) * KS * KS * KS;
-    const Plan3T p2 = plan3_fwdtap2(M, K, C, KS);
-    if (p2.tile) return bytes3(p2.splits, M, K, Kg, 1);
-    return bytes3(plan3(pick3(M, K, 1), M, K, Kg, 1), M, K, Kg, 1);
+    return slab_bytes(choose_fwd3(shape3_of_features(N, C, K, OD, OH, OW), KS, kIdeal), (long long)N * OD * OH * OW, K);
 }
 
 size_t gz_conv3d_dgrad_workspace_bytes(int N, int C, int K, int OD, int OH, int OW, int KS) {
-    long long M = (long long)N * OD * OH * OW;      // per phase: the S = 2 output grid has OD*OH*OW cells per phase
-    const Plan3T p2 = plan3_dgtap2(M, C, K, KS, 2, 1);
-    if (p2.tile) return p2.splits > 1 ? (size_t)p2.slabs * M * C * 4 : 0;
-    DgPlan3 pl = plan3_dg(pick3(M, C, 8), M, C, K, KS, 2, 1);
-    return pl.splits > 1 ? (size_t)pl.slabs * M * C * 4 : 0;
+    return slab_bytes(choose_dgrad3(shape3_of_features(N, C, K, OD, OH, OW), KS, kS3, kP3, kIdeal),
+                      (long long)N * OD * OH * OW, C);
+}
+
+// (in asked splits, not slabs: wg_fit_splits clamps in that unit)
+size_t gz_conv3d_wgrad_workspace_bytes(int N, int C, int K, int OD, int OH, int OW, int KS) {
+    const Choice c = choose_wgrad3(shape3_of_features(N, C, K, OD, OH, OW), KS, kIdeal);
+    return c.splits > 1 ? (size_t)c.splits * K * C * KS * KS * KS * 4 : 0;
 }
 
 int gz_conv3d_fwd(const float* x, const float* wpack, const float* bias, float* y, float* workspace, size_t ws_bytes,
@@ -499,22 +526,8 @@ int gz_conv3d_fwd(const float* x, const float* wpack, const float* bias, float* 
     if (!shape3_ok(s, KS, S, P)) return GZ_ERR_BAD_SHAPE;
     if (big3((long long)N * C * D * H * W) || big3((long long)N * K * OD * OH * OW)) return GZ_ERR_TOO_LARGE;
     if (((uintptr_t)wpack & 15) || ((uintptr_t)y & 15)) return GZ_ERR_BAD_SHAPE;
-    const int kdim = (fwd3_tap_major(C) ? round_bk(C) : C) * 27;
-    const Plan3T p2 = plan3_fwdtap2((long long)N * OD * OH * OW, K, C, KS);
-    if (p2.tile && !((uintptr_t)x & 3)) {
-        int sp = p2.splits;
-        if (sp > 1 && (!workspace || ws_bytes < bytes3(sp, (long long)N * OD * OH * OW, K, kdim, 1))) return GZ_ERR_WORKSPACE;
-        float* sl = sp > 1 ? workspace : nullptr;
-        return p2.tile == 1 ? run_fwdtap3<C3_256x128, 3, 2, 1>(x, wpack, bias, y, s, act, slope, stream, sp, sl)
-                            : run_fwdtap3<C3_256x64, 3, 2, 1>(x, wpack, bias, y, s, act, slope, stream, sp, sl);
-    }
-    int t = pick3((long long)N * OD * OH * OW, K, 1);
-    int splits = plan3(t, (long long)N * OD * OH * OW, K, kdim, 1);
-    if (splits > 1 && (!workspace || ws_bytes < bytes3(splits, (long long)N * OD * OH * OW, K, kdim, 1))) splits = 1;
-    float* slab = splits > 1 ? workspace : nullptr;
-#define CALL(CFG) run_fwd3<CFG, 3, 2, 1>(x, wpack, bias, y, s, act, slope, stream, splits, slab)
-    GZ3_TILE_SWITCH(t, CALL)
-#undef CALL
+    const Facts f = facts_of(x, y, workspace, ws_bytes, bias || act != ACT_NONE, false);
+    return launch_fwd3<3, 2, 1>(choose_fwd3(s, KS, f), x, wpack, bias, y, s, act, slope, workspace, stream);
 }
 
 int gz_conv3d_dgrad(const float* y, const float* wpack, const float* bias, float* x, float* workspace,
@@ -526,33 +539,8 @@ int gz_conv3d_dgrad(const float* y, const float* wpack, const float* bias, float
     if (!shape3_ok(s, KS, S, P) || D % S || H % S || W % S) return GZ_ERR_BAD_SHAPE;
     if (big3((long long)N * C * D * H * W) || big3((long long)N * K * OD * OH * OW)) return GZ_ERR_TOO_LARGE;
     if ((uintptr_t)wpack & 15) return GZ_ERR_BAD_SHAPE;
-    const long long Mp = (long long)N * (D / S) * (H / S) * (W / S);
-    if (dg3_tap2(K, C)) {       // (the packed image is tap-major: this path or none)
-        const Plan3T p2 = plan3_dgtap2(Mp, C, K, KS, S, P);
-        if (!p2.tile) return GZ_ERR_UNSUPPORTED;
-        if (p2.splits > 1 && (!workspace || ws_bytes < (size_t)p2.slabs * Mp * C * 4)) return GZ_ERR_WORKSPACE;
-        float* sl = p2.splits > 1 ? workspace : nullptr;
-        return p2.tile == 1 ? run_dgradtap3<C3_256x128, 3, 2, 1>(y, wpack, bias, x, s, act, slope, stream, p2.splits, sl)
-                            : run_dgradtap3<C3_256x64, 3, 2, 1>(y, wpack, bias, x, s, act, slope, stream, p2.splits, sl);
-    }
-    int t = pick3(Mp, C, S * S * S);
-    DgPlan3 pl = plan3_dg(t, Mp, C, K, KS, S, P);
-    int splits = pl.splits;
-    if (splits > 1 && (!workspace || ws_bytes < (size_t)pl.slabs * Mp * C * 4)) splits = 1;
-    float* slab = splits > 1 ? workspace : nullptr;
-#define CALL(CFG) run_dgrad3<CFG, 3, 2, 1>(y, wpack, bias, x, s, act, slope, stream, splits, slab)
-    GZ3_TILE_SWITCH(t, CALL)
-#undef CALL
-}
-
-size_t gz_conv3d_wgrad_workspace_bytes(int N, int C, int K, int OD, int OH, int OW, int KS) {
-    long long count = (long long)K * C * KS * KS * KS;
-    int chunks = (N * OD * OH * OW + BK - 1) / BK;
-    long long tiles = (long long)((K + 127) / 128) * ((C * KS * KS * KS + 127) / 128);
-    int splits = splits3(tiles, chunks);
-    const Conv3DShape s{N, C, 2 * OD, 2 * OH, 2 * OW, K, OD, OH, OW};
-    if (wg3r_ok(s)) splits = wg3r_splits(s, KS);
-    return splits > 1 ? (size_t)splits * count * 4 : 0;
+    const Facts f = facts_of(y, x, workspace, ws_bytes, bias || act != ACT_NONE, false);
+    return launch_dgrad3<3, 2, 1>(choose_dgrad3(s, KS, S, P, f), y, wpack, bias, x, s, act, slope, workspace, stream);
 }
 
 int gz_conv3d_wgrad(const float* x, const float* y, float* dw, float* workspace, size_t ws_bytes, int N, int C, int D,
@@ -562,16 +550,24 @@ int gz_conv3d_wgrad(const float* x, const float* y, float* dw, float* workspace,
     if (KS != 3 || S != 2 || P != 1) return GZ_ERR_UNSUPPORTED;
     if (!shape3_ok(s, KS, S, P)) return GZ_ERR_BAD_SHAPE;
     if (big3((long long)N * C * D * H * W) || big3((long long)N * K * OD * OH * OW)) return GZ_ERR_TOO_LARGE;
-    if (wg3r_ok(s))
-        return K >= 256 ? run_wgrad3r<C3_256x128, 3, 2, 1>(x, y, dw, workspace, ws_bytes, s, stream)
-                        : run_wgrad3r<C3_128x256, 3, 2, 1>(x, y, dw, workspace, ws_bytes, s, stream);
-    long long NTOT = (long long)C * KS * KS * KS;
-    int t = NTOT <= 32 ? 2 : ((NTOT <= 64 || K <= 64) ? (K <= 64 ? 3 : 1) : 0);
-    const int force = knobs().wg3_tile;      // experiment
-    if (force >= 0 && t == 0) t = force;
-#define CALL(CFG) run_wgrad3<CFG, 3, 2, 1>(x, y, dw, workspace, ws_bytes, s, stream)
-    GZ3_TILE_SWITCH(t, CALL)
-#undef CALL
+    const Facts f = facts_of((const void*)((uintptr_t)x | (uintptr_t)y), dw, workspace, ws_bytes, false, false);
+    return launch_wgrad3<3, 2, 1>(choose_wgrad3(s, KS, f), x, y, dw, workspace, s, stream);
+}
+
+/* Which kernel a launch of op (0 F, 1 Dg, 2 Wg) takes, as text: the choice for 16-byte aligned tensors and a workspace
+ * of the advertised size.  Runs on the CPU (no HIP call); pinned by tests/test_dispatch_plan.py. */
+int gz_conv3d_plan(int op, int N, int C, int D, int H, int W, int K, int OD, int OH, int OW, int KS, int S, int P,
+                   char* buf, int buflen) {
+    if (!buf || buflen <= 0) return GZ_ERR_BAD_SHAPE;
+    buf[0] = 0;
+    Conv3DShape s{N, C, D, H, W, K, OD, OH, OW};
+    if (KS != 3 || S != 2 || P != 1) return GZ_ERR_UNSUPPORTED;
+    if (!shape3_ok(s, KS, S, P) || op < 0 || op > 2 || (op == 1 && (D % S || H % S || W % S))) return GZ_ERR_BAD_SHAPE;
+    const Choice c = op == 0 ? choose_fwd3(s, KS, kIdeal) : op == 1 ? choose_dgrad3(s, KS, S, P, kIdeal)
+                                                                     : choose_wgrad3(s, KS, kIdeal);
+    return snprintf(buf, (size_t)buflen, "%s %s<%s> %s splits=%d slabs=%d", op == 0 ? "F" : op == 1 ? "Dg" : "Wg",
+                    c.kind == KIgemm ? "igemm" : c.kind == KIgemm2 ? "igemm2" : "igemm2r", tile_text(c.tile),
+                    loader_text3(op, c), c.splits, c.slabs);
 }
 
 }  // extern "C"

@@ -1,10 +1,11 @@
 """Writes tests/golden/dispatch_plan.json: which kernel / tile / loaders / slab count every convolution layer of the
-BASELINE.json configurations dispatches to (gz_conv2d_plan, pure host logic of libgz_hip.so -- runs without a GPU).
+BASELINE.json configurations dispatches to (gz_conv2d_plan / gz_conv3d_plan, pure host logic of libgz_hip.so -- runs
+without a GPU).
 
     python tests/golden/make_dispatch_golden.py            # regenerate after a DELIBERATE heuristic change
 
-tests/test_dispatch_plan.py compares the library against this table, so an edit of a threshold in csrc/gz_conv.hip
-that moves a layer to another kernel shows up as a diff of this file."""
+tests/test_dispatch_plan.py compares the library against this table, so an edit of a threshold in csrc/gz_conv.hip or
+csrc/gz_conv3d.hip that moves a layer to another kernel shows up as a diff of this file."""
 import ctypes
 import json
 import os
@@ -42,13 +43,20 @@ HOLOGAN_LAYERS_128 = [
     ("D.blocks2 256->512 @16 k5", 256, 512, 16, 5, 2, 2),
     ("G.final(EXT-128) 64->3 @64->128 (adjoint)", 3, 64, 128, 4, 2, 1),
 ]
+# (name, C_image_side, K_feature_side, D (image side)): the Conv3d view of the generator's two ConvTranspose3d k3 s2 p1
+# op1 layers (core/models/hologan_generator.py: block1 in_planes*8 -> in_planes*2 on the 4^3 constant, block2 in_planes*2
+# -> in_planes, in_planes = 64), the same in both HoloGAN configurations
+HOLOGAN_LAYERS_3D = [
+    ("G.block1 512->128 @4->8 3d (adjoint)", 128, 512, 8),
+    ("G.block2 128->64 @8->16 3d (adjoint)", 64, 128, 16),
+]
 CONFIGS = [
-    ("dc_gan bs=64 (config 1)", 64, DCGAN_LAYERS),
-    ("dc_gan bs=128 (metric)", 128, DCGAN_LAYERS),
-    ("dc_gan bs=512 (configs 2, 4)", 512, DCGAN_LAYERS),
-    ("wgan_gp bs=256 (config 3)", 256, DCGAN_LAYERS),
-    ("hologan bs=64 @64x64 (config 5, parity-pinned size)", 64, HOLOGAN_LAYERS_64),
-    ("hologan bs=64 @128x128 (config 5, EXT-128)", 64, HOLOGAN_LAYERS_128),
+    ("dc_gan bs=64 (config 1)", 64, DCGAN_LAYERS, []),
+    ("dc_gan bs=128 (metric)", 128, DCGAN_LAYERS, []),
+    ("dc_gan bs=512 (configs 2, 4)", 512, DCGAN_LAYERS, []),
+    ("wgan_gp bs=256 (config 3)", 256, DCGAN_LAYERS, []),
+    ("hologan bs=64 @64x64 (config 5, parity-pinned size)", 64, HOLOGAN_LAYERS_64, HOLOGAN_LAYERS_3D),
+    ("hologan bs=64 @128x128 (config 5, EXT-128)", 64, HOLOGAN_LAYERS_128, HOLOGAN_LAYERS_3D),
 ]
 OPS = ("F", "Dg", "Wg")
 
@@ -57,7 +65,7 @@ def plan_table():
     from lightning_gan_zoo_amd._lib import lib
     table = {}
     buf = ctypes.create_string_buffer(512)
-    for cfg, bs, layers in CONFIGS:
+    for cfg, bs, layers, layers3d in CONFIGS:
         rows = {}
         for name, C, K, H, KH, S, P in layers:
             OH = (H + 2 * P - KH) // S + 1
@@ -65,6 +73,12 @@ def plan_table():
                 rc = lib.gz_conv2d_plan(op, bs, C, H, H, K, OH, OH, KH, KH, S, P, buf, 512)
                 if rc < 0:
                     raise RuntimeError("gz_conv2d_plan failed for %s / %s: %d" % (cfg, name, rc))
+                rows["%s | %s" % (name, OPS[op])] = buf.value.decode()
+        for name, C, K, D in layers3d:
+            for op in range(3):
+                rc = lib.gz_conv3d_plan(op, bs, C, D, D, D, K, D // 2, D // 2, D // 2, 3, 2, 1, buf, 512)
+                if rc < 0:
+                    raise RuntimeError("gz_conv3d_plan failed for %s / %s: %d" % (cfg, name, rc))
                 rows["%s | %s" % (name, OPS[op])] = buf.value.decode()
         table[cfg] = rows
     return table

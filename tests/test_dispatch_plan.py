@@ -1,8 +1,8 @@
-"""The dispatch is pinned: gz_conv2d_plan -- the library's own description of the kernel, tile,
-operand loaders and slab count a launch takes, pure host logic -- must reproduce tests/golden/dispatch_plan.json for
-every convolution layer of the five BASELINE configurations.  A threshold edit in csrc/gz_conv.hip that silently moves
-a layer onto a slower kernel (parity stays green) fails here; a deliberate change regenerates the table
-(python tests/golden/make_dispatch_golden.py) and shows up as its diff."""
+"""The dispatch is pinned: gz_conv2d_plan / gz_conv3d_plan -- the library's own description of the
+kernel, tile, operand loaders and slab count a launch takes, pure host logic -- must reproduce
+tests/golden/dispatch_plan.json for every convolution layer of the five BASELINE configurations.  A threshold edit in
+csrc/gz_conv.hip or csrc/gz_conv3d.hip that silently moves a layer onto a slower kernel (parity stays green) fails here;
+a deliberate change regenerates the table (python tests/golden/make_dispatch_golden.py) and shows up as its diff."""
 import json
 import os
 import sys
@@ -40,6 +40,23 @@ def test_the_heavy_layers_are_on_the_hand_ordered_skeleton():
     m = golden["dc_gan bs=128 (metric)"]
     assert m["G.out 128->3 @32->64 (adjoint) | Dg"].startswith("Dg direct dgrad_smallc4_k4s2p1<C=3,KS=8>")
     assert m["D.conv_in 3->64 @64 | Wg"].startswith("Wg direct wgrad_k4s2p1_fewc<mfma16x16x4,C=3,KT=4>")
+
+
+def test_hologans_3d_layers_are_on_the_skeletons_they_were_measured_on():
+    """HoloGAN's two ConvTranspose3d layers at bs 64 (gz_conv3d_plan), the same in both configurations: block1 (512 ->
+    128) runs all three directions on the igemm2 family, its transposed launch with 27 slabs over the 8 phases; block2
+    (128 -> 64) has 64 GEMM columns in the transposed direction, which stays on the igemm kernel (csrc/gz_conv3d.hip:
+    dg3_tap2), and takes igemm2 / igemm2r for the other two."""
+    golden = json.load(open(os.path.join(HERE, "golden", "dispatch_plan.json")))
+    for cfg in ("hologan bs=64 @64x64 (config 5, parity-pinned size)", "hologan bs=64 @128x128 (config 5, EXT-128)"):
+        t = golden[cfg]
+        b1, b2 = "G.block1 512->128 @4->8 3d (adjoint)", "G.block2 128->64 @8->16 3d (adjoint)"
+        assert t[b1 + " | Dg"].startswith("Dg igemm2<256x128> Conv3DDgTapA2") and t[b1 + " | Dg"].endswith("slabs=27")
+        assert t[b1 + " | F"].startswith("F igemm2<256x128> Conv3DTapA2")
+        assert t[b1 + " | Wg"].startswith("Wg igemm2r<256x128>")
+        assert t[b2 + " | Dg"].startswith("Dg igemm<128x64> Conv3DDgALoader splits=1")
+        assert t[b2 + " | F"].startswith("F igemm2<256x64> Conv3DTapA2")
+        assert t[b2 + " | Wg"].startswith("Wg igemm2r<128x256>")
 
 
 def test_environment_switches_are_ignored_without_gz_experiments():

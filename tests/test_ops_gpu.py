@@ -1727,3 +1727,146 @@ def test_conv_missing_workspace_contract():
     stats = torch.empty((lib.gz_conv2d_dgrad_stats_rows(*shape), C, 2), device="cuda")
     assert lib.gz_conv2d_dgrad_stats_ws(_p(gyd), _p(_packed(wd, "d", g)), _p(dx), _p(stats), None, 0, *shape, _stream()) == -3
     torch.cuda.synchronize()
+
+
+# ---------------------------------------------------------------------------
+# conv3d through the C ABI: what each skeleton does with a short workspace (include/gz_ops.h)
+# ---------------------------------------------------------------------------
+def _c3_ref(case):
+    """ConvTranspose3d(k3, s2, p1, op1) on the CPU for one (N, Cin, D, Cout) of test_conv3d_family: the feature map x,
+    weight w, output gradient go, and the reference's output, input gradient and weight gradient."""
+    N, Cin, D, Cout = case
+    torch.set_num_threads(min(16, torch.get_num_threads()))
+    x, w = rnd(N, Cin, D, D, D, seed=81), rnd(Cin, Cout, 3, 3, 3, seed=82, scale=0.1)
+    xr, wr = x.clone().requires_grad_(), w.clone().requires_grad_()
+    out = TF.conv_transpose3d(xr, wr, None, stride=2, padding=1, output_padding=1)
+    go = rnd(*out.shape, seed=83)
+    out.backward(go)
+    return x, w, go, out.detach(), xr.grad, wr.grad
+
+
+def _c3_plan(op, case):
+    import ctypes
+    from lightning_gan_zoo_amd._lib import lib
+    N, Cin, D, Cout = case
+    buf = ctypes.create_string_buffer(256)
+    assert lib.gz_conv3d_plan(op, N, Cout, 2 * D, 2 * D, 2 * D, Cin, D, D, D, 3, 2, 1, buf, 256) > 0
+    return buf.value.decode()
+
+
+def _c3_shape(case):
+    """The C ABI's shape arguments: image side (C, 2D) first, feature side (K, D) second, then KS, S, P."""
+    N, Cin, D, Cout = case
+    return (N, Cout, 2 * D, 2 * D, 2 * D, Cin, D, D, D, 3, 2, 1)
+
+
+def _c3_ws(nbytes):
+    return torch.empty(max(nbytes // 4, 1), device="cuda")
+
+
+def test_conv3d_transposed_igemm2_refuses_a_short_workspace():
+    """A split transposed launch on the igemm2 skeleton, without a workspace or with one a byte short: GZ_ERR_WORKSPACE,
+    nothing launched (the output keeps its sentinel); with the advertised workspace it matches the reference."""
+    F = _F()
+    from lightning_gan_zoo_amd._lib import lib
+    from lightning_gan_zoo_amd.functional._base import _p, _packed3, _stream
+    case = (8, 512, 4, 128)
+    assert _c3_plan(1, case) == "Dg igemm2<256x128> Conv3DDgTapA2(gather, LDS-DMA 4B) splits=8 slabs=27"
+    N, Cin, D, Cout = case
+    x, w, _, ref, _, _ = _c3_ref(case)
+    xd, wp = x.cuda(), _packed3(w.cuda(), "d")
+    nbytes = lib.gz_conv3d_dgrad_workspace_bytes(N, Cout, Cin, D, D, D, 3)
+    assert nbytes == 27 * N * D ** 3 * Cout * 4
+    ws = _c3_ws(nbytes)
+    out = torch.full(ref.shape, 7.5, device="cuda")
+    for wsp, nb in ((None, 0), (_p(ws), nbytes - 1)):
+        rc = lib.gz_conv3d_dgrad(_p(xd), _p(wp), None, _p(out), wsp, nb, *_c3_shape(case), F.ACT_NONE, 0.0, _stream())
+        torch.cuda.synchronize()
+        assert rc == -3
+        assert bool((out == 7.5).all())
+    rc = lib.gz_conv3d_dgrad(_p(xd), _p(wp), None, _p(out), _p(ws), nbytes, *_c3_shape(case), F.ACT_NONE, 0.0, _stream())
+    assert rc == 0 and rel(out, ref) < TOL
+
+
+def test_conv3d_transposed_igemm_runs_unsplit_without_a_workspace():
+    """A split transposed launch on igemm (130 columns: not a multiple of the tile): without a workspace it runs unsplit."""
+    F = _F()
+    from lightning_gan_zoo_amd._lib import lib
+    from lightning_gan_zoo_amd.functional._base import _p, _packed3, _stream
+    case = (2, 128, 4, 130)
+    assert _c3_plan(1, case) == "Dg igemm<64x64> Conv3DDgALoader splits=8 slabs=27"
+    N, Cin, D, Cout = case
+    x, w, _, ref, _, _ = _c3_ref(case)
+    xd, wp = x.cuda(), _packed3(w.cuda(), "d")
+    nbytes = lib.gz_conv3d_dgrad_workspace_bytes(N, Cout, Cin, D, D, D, 3)
+    assert nbytes == 27 * N * D ** 3 * Cout * 4
+    for ws, nb in ((None, 0), (_c3_ws(nbytes), nbytes)):
+        out = torch.empty(ref.shape, device="cuda")
+        rc = lib.gz_conv3d_dgrad(_p(xd), _p(wp), None, _p(out), _p(ws) if ws is not None else None, nb, *_c3_shape(case),
+                                 F.ACT_NONE, 0.0, _stream())
+        assert rc == 0 and rel(out, ref) < TOL, nb
+
+
+@pytest.mark.parametrize("case,plan", [((64, 512, 4, 128), "F igemm2<256x128> Conv3DTapA2(gather, LDS-DMA 4B) splits=4 slabs=4"),
+                                       ((3, 20, 4, 12), "F igemm<128x32> Conv3DFwdALoader splits=2 slabs=2")])
+def test_conv3d_forward_short_workspace(case, plan):
+    """The plain strided form (the transposed layer's input gradient), split, one shape per skeleton: igemm2 refuses a
+    missing or short workspace and launches nothing, igemm runs unsplit; both match with the advertised workspace."""
+    F = _F()
+    from lightning_gan_zoo_amd._lib import lib
+    from lightning_gan_zoo_amd.functional._base import _p, _packed3, _stream
+    assert _c3_plan(0, case) == plan
+    N, Cin, D, Cout = case
+    x, w, go, _, ref_dx, _ = _c3_ref(case)
+    god, wp = go.cuda(), _packed3(w.cuda(), "f")
+    nbytes = lib.gz_conv3d_fwd_workspace_bytes(N, Cout, Cin, D, D, D, 3)
+    assert nbytes == int(plan.rsplit("=", 1)[1]) * N * D ** 3 * Cin * 4
+    ws = _c3_ws(nbytes)
+    out = torch.full(ref_dx.shape, 7.5, device="cuda")
+    for wsp, nb in ((None, 0), (_p(ws), nbytes - 1)):
+        rc = lib.gz_conv3d_fwd(_p(god), _p(wp), None, _p(out), wsp, nb, *_c3_shape(case), F.ACT_NONE, 0.0, _stream())
+        torch.cuda.synchronize()
+        if "igemm2" in plan:
+            assert rc == -3
+            assert bool((out == 7.5).all())
+        else:
+            assert rc == 0 and rel(out, ref_dx) < TOL, nb
+            out.fill_(7.5)
+    rc = lib.gz_conv3d_fwd(_p(god), _p(wp), None, _p(out), _p(ws), nbytes, *_c3_shape(case), F.ACT_NONE, 0.0, _stream())
+    assert rc == 0 and rel(out, ref_dx) < TOL
+
+
+@pytest.mark.parametrize("case,plan", [((8, 128, 8, 64), "Wg igemm2r<128x256> WgALoader+Wg3DBLoader(register-staged) splits=10 slabs=10"),
+                                       ((4, 64, 8, 16), "Wg igemm<64x64> WgALoader+Wg3DBLoader splits=16 slabs=16")])
+def test_conv3d_weight_gradient_fits_its_splits_to_the_workspace(case, plan):
+    """Both weight-gradient skeletons with the advertised workspace, with room for exactly two slabs, and with none."""
+    from lightning_gan_zoo_amd._lib import lib
+    from lightning_gan_zoo_amd.functional._base import _p, _stream
+    assert _c3_plan(2, case) == plan
+    N, Cin, D, Cout = case
+    x, w, go, _, _, ref_dw = _c3_ref(case)
+    xd, god = x.cuda(), go.cuda()
+    count = Cin * Cout * 27
+    nbytes = lib.gz_conv3d_wgrad_workspace_bytes(N, Cout, Cin, D, D, D, 3)
+    assert nbytes == int(plan.split("splits=")[1].split()[0]) * count * 4      # sized in splits: the clamp's unit
+    for nb in (nbytes, 2 * count * 4, 0):
+        ws = _c3_ws(nb)
+        dw = torch.empty(ref_dw.shape, device="cuda")
+        rc = lib.gz_conv3d_wgrad(_p(god), _p(xd), _p(dw), _p(ws) if nb else None, nb, *_c3_shape(case), _stream())
+        assert rc == 0 and rel(dw, ref_dw) < TOL, nb
+
+
+def test_conv3d_packed_weights_must_be_16_byte_aligned():
+    """wpack 4 bytes off a 16-byte boundary: GZ_ERR_BAD_SHAPE from the forward and the transposed launcher."""
+    F = _F()
+    from lightning_gan_zoo_amd._lib import lib
+    from lightning_gan_zoo_amd.functional._base import _p, _packed3, _stream
+    case = (2, 8, 4, 4)
+    x, w, go, ref, ref_dx, _ = _c3_ref(case)
+    wd = w.cuda()
+    wf, wt = _offset_view(_packed3(wd, "f")), _offset_view(_packed3(wd, "d"))
+    assert wf.data_ptr() % 16 == 4 and wt.data_ptr() % 16 == 4
+    y, out = torch.empty(ref_dx.shape, device="cuda"), torch.empty(ref.shape, device="cuda")
+    assert lib.gz_conv3d_fwd(_p(go.cuda()), _p(wf), None, _p(y), None, 0, *_c3_shape(case), F.ACT_NONE, 0.0, _stream()) == -1
+    assert lib.gz_conv3d_dgrad(_p(x.cuda()), _p(wt), None, _p(out), None, 0, *_c3_shape(case), F.ACT_NONE, 0.0, _stream()) == -1
+    torch.cuda.synchronize()
