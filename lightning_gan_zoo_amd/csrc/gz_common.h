@@ -72,6 +72,28 @@ __device__ __forceinline__ double wave_sum_d(double v) {
     return v;
 }
 
+// Raw buffer loads: a voffset >= num_records (OOB for one) reads as 0 without a branch.
+constexpr uint32_t OOB = 0x80000000u;  // voffset that is out of range for every tensor (< 2 GiB)
+
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* p, uint32_t bytes) {
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, (int)bytes, 0x00020000);
+}
+__device__ __forceinline__ float bload(__amdgpu_buffer_rsrc_t r, uint32_t voff, uint32_t soff) {
+    return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, voff, soff, 0));
+}
+__device__ __forceinline__ f32x4 bload4(__amdgpu_buffer_rsrc_t r, uint32_t voff, uint32_t soff) {
+    return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0));
+}
+
+// 2-D convolution geometry
+// x: [N, C, H, W]   ("image side": conv input, dgrad output)
+// y: [N, K, OH, OW] ("feature side": conv output, dgrad input)
+// w: [K, C, KH, KW] (Conv2d weight; a ConvTranspose2d weight [Cin_T, Cout_T, KH, KW]
+//                    is the same array with K = Cin_T, C = Cout_T)
+struct ConvShape {
+    int N, C, H, W, K, OH, OW;
+};
+
 inline const char*& last_error_slot() {
     static thread_local const char* msg = "";
     return msg;

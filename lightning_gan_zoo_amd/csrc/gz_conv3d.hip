@@ -9,6 +9,7 @@
 #include <type_traits>
 
 #include "gz_conv_choice.h"
+#include "gz_igemm.h"
 #include "../../include/gz_ops.h"
 
 namespace gz {

@@ -1,25 +1,12 @@
-// The vocabulary of a launch choice, shared by gz_conv.hip (conv2d) and gz_conv3d.hip (conv3d): tile configurations and
-// their ids, skeleton kinds, loaders, the facts only a call knows, and the Choice the choose_* functions of both files
-// return.  choose_* answers "which kernel does this launch take" once per op: launch_* switch on the answer, the
-// workspace sizes are read from it, gz_conv2d_plan / gz_conv3d_plan print it.
+// The vocabulary of a launch choice, shared by gz_conv.hip (conv2d), its direct kernels (gz_conv_direct.hip) and
+// gz_conv3d.hip (conv3d): tile ids, skeleton kinds, loaders, the facts only a call knows, and the Choice the choose_*
+// functions of both dispatchers return.  choose_* answers "which kernel does this launch take" once per op: launch_*
+// switch on the answer, the workspace sizes are read from it, gz_conv2d_plan / gz_conv3d_plan print it.  Plain host
+// data: no skeleton is included here (the tile configurations the ids stand for are in gz_igemm.h).
 #pragma once
-#include "gz_igemm.h"
+#include "gz_common.h"
 
 namespace gz {
-
-using Cfg128x128 = TileCfg<2, 2, 2, 2>;
-using Cfg128x64 = TileCfg<2, 2, 2, 1>;
-using Cfg128x32 = TileCfg<4, 1, 1, 1>;
-using Cfg64x64 = TileCfg<2, 2, 1, 1>;
-
-// round 3 (gz_igemm.h, igemm2): one wavefront per SIMD, 128x128 / 128x64 accumulators per wavefront
-using Cfg256x256 = TileCfg2<2, 2, 4, 1>;
-using Cfg256x128 = TileCfg2<2, 2, 2, 2>;
-using Cfg512x64 = TileCfg2<4, 1, 2, 2>;       // 64 output channels in all (D.block1-size input gradients)
-using Cfg128x256 = TileCfg2<1, 4, 2, 2>;      // weight gradient with 128 output channels
-// round 4: 256 x 64 (wavefronts 2 x 2 of 128 x 32, 64 accumulator registers): twice the tiles of 256x128 for launches
-// that would otherwise put one workgroup on a CU or split their reduction; three workgroups per CU (37-42 KB of LDS)
-using Cfg256x64 = TileCfg2<2, 2, 1, 3>;
 
 enum TileId { T128x128 = 0, T128x64 = 1, T128x32 = 2, T64x64 = 3, T256x256 = 4, T256x128 = 5, T512x64 = 6, T128x256 = 7,
               T256x64 = 8,
@@ -89,5 +76,15 @@ inline int wg_fit_splits(int splits, size_t ws_bytes, long long count) {
     const long long max_splits = (long long)(ws_bytes / 4) / count;
     return max_splits < 2 ? 1 : (splits > max_splits ? (int)max_splits : splits);
 }
+
+
+// what every conv2d entry point checks of its arguments before it chooses
+inline bool shape_ok(const ConvShape& s, int KH, int KW, int S, int P) {
+    if (s.N <= 0 || s.C <= 0 || s.K <= 0 || s.H <= 0 || s.W <= 0) return false;
+    if (s.OH != (s.H + 2 * P - KH) / S + 1 || s.OW != (s.W + 2 * P - KW) / S + 1) return false;
+    return true;
+}
+
+inline bool too_large(long long elems) { return elems * 4 >= (1ll << 31); }
 
 }  // namespace gz

@@ -34,3 +34,22 @@
 //   gz_igemm2.h           the igemm2 skeleton (rounds 3-5): igemm2 / igemm2w / igemm2r kernels, their loaders, launchers
 #pragma once
 #include "gz_igemm2.h"
+
+namespace gz {
+
+// the tile configurations the convolution dispatchers launch (their ids: TileId, gz_conv_choice.h)
+using Cfg128x128 = TileCfg<2, 2, 2, 2>;
+using Cfg128x64 = TileCfg<2, 2, 2, 1>;
+using Cfg128x32 = TileCfg<4, 1, 1, 1>;
+using Cfg64x64 = TileCfg<2, 2, 1, 1>;
+
+// round 3 (igemm2, gz_igemm2.h): one wavefront per SIMD, 128x128 / 128x64 accumulators per wavefront
+using Cfg256x256 = TileCfg2<2, 2, 4, 1>;
+using Cfg256x128 = TileCfg2<2, 2, 2, 2>;
+using Cfg512x64 = TileCfg2<4, 1, 2, 2>;       // 64 output channels in all (D.block1-size input gradients)
+using Cfg128x256 = TileCfg2<1, 4, 2, 2>;      // weight gradient with 128 output channels
+// round 4: 256 x 64 (wavefronts 2 x 2 of 128 x 32, 64 accumulator registers): twice the tiles of 256x128 for launches
+// that would otherwise put one workgroup on a CU or split their reduction; three workgroups per CU (37-42 KB of LDS)
+using Cfg256x64 = TileCfg2<2, 2, 1, 3>;
+
+}  // namespace gz

@@ -448,7 +448,7 @@ struct ConvDg5A2 {
 };
 
 // B operand of ConvDg5A2: image [24 k rows][128 columns = (phase j = 2 py + px, 32 channels)] per chunk of 8 LDS rows
-// r = (ty, ko), gathered row-wise out of the tap-major dgrad pack of a 5x5 s2 p2 weight (gz_conv.hip pack_dgrad_tap_body:
+// r = (ty, ko), gathered row-wise out of the tap-major dgrad pack of a 5x5 s2 p2 weight (gz_pack.hip pack_dgrad_tap_body:
 // phase (py, px) at phase * 9 * K * ldc floats, row (ty * nx + tx) * K + ko, nx = 3 - px): rows 0-15 = (r, tx in {0, 1}) of
 // every phase that has tap row ty (py = 1 has none at ty = 2: zeros, never multiplied), rows 16-23 = (r, tx = 2) of the
 // px = 0 phases.  A piece = two image rows x 128 columns (lane = (image row, 4 columns)); the lane's phase and tap offsets

@@ -3,28 +3,14 @@
 #pragma once
 #include "gz_common.h"
 #include "gz_knobs.h"
+#include "gz_pack_layout.h"
 #include <type_traits>
 
 namespace gz {
 
 constexpr int NT = 256;
-constexpr int BK = 16;
-// number of kernel taps k = ((parity + P) % S) + S*t below KS that a transposed-conv output phase of that parity has
-__host__ __device__ constexpr int dg_taps(int KS, int S, int P, int parity) {
-    return (KS - ((parity + P) % S) + S - 1) / S;
-}
-
-constexpr uint32_t OOB = 0x80000000u;  // voffset that is out of range for every tensor (< 2 GiB)
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* p, uint32_t bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, (int)bytes, 0x00020000);
-}
-__device__ __forceinline__ float bload(__amdgpu_buffer_rsrc_t r, uint32_t voff, uint32_t soff) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, voff, soff, 0));
-}
-__device__ __forceinline__ f32x4 bload4(__amdgpu_buffer_rsrc_t r, uint32_t voff, uint32_t soff) {
-    return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0));
-}
+// (BK, dg_taps and round_bk are in gz_pack_layout.h; the raw buffer loads and ConvShape in gz_common.h: the direct
+// kernels of gz_conv_direct.hip and the packers of gz_pack.hip use them without this header)
 
 // LDS-DMA (buffer_load ... lds): the wave's 64 lanes land at lds_base + lane*size, no VGPR staging and no
 // ds_write; lds_base must be wave-uniform.  Out-of-range lanes write 0.
@@ -227,16 +213,8 @@ struct KContigLoader {
 };
 
 // ---------------------------------------------------------------------------
-// convolution geometry
+// convolution geometry (ConvShape: gz_common.h)
 // ---------------------------------------------------------------------------
-// x: [N, C, H, W]   ("image side": conv input, dgrad output)
-// y: [N, K, OH, OW] ("feature side": conv output, dgrad input)
-// w: [K, C, KH, KW] (Conv2d weight; a ConvTranspose2d weight [Cin_T, Cout_T, KH, KW]
-//                    is the same array with K = Cin_T, C = Cout_T)
-struct ConvShape {
-    int N, C, H, W, K, OH, OW;
-};
-
 // A operand of the forward GEMM: A[m = (n, oy, ox)][k = (c, ky, kx)] = x[n][c][oy*S-P+ky][ox*S-P+kx]
 template <int BM, int KH, int KW, int S, int P>
 struct ConvFwdALoader {
@@ -329,7 +307,6 @@ struct ConvFwdALoader {
 // advance through the wave-uniform scalar offset, and the padding test is one compare pair per chunk.
 // The descriptor base is moved back by the largest negative tap shift so that voffsets stay non-negative; taps
 // in the padding use the out-of-range voffset and are never dereferenced.
-constexpr int round_bk(int v) { return (v + BK - 1) / BK * BK; }
 
 // A[m = (n, oy, ox)][k = (tap, c)] = x[n][c][oy*S-P+ky][ox*S-P+kx]
 template <int BM, int KH, int KW, int S, int P>

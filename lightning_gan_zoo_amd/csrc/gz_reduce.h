@@ -1,8 +1,13 @@
-// The slab sum shared by gz_reduce_multi (gz_conv.hip) and the fused optimizers that read unreduced weight-gradient slabs
-// directly (gz_optim.hip): ONE definition of the summation order, so that "reduce, then step" and "step from the slabs"
-// give the same bits.  A workgroup of four wavefronts owns 64 float4: wavefront w takes slabs w, w+4, ... of source 0,
-// then of source 1, ... (four independent accumulators per lane), the four partial sums meet in LDS in wavefront order.
-// The result is valid in wavefront 0.
+// What the units share of the weight-gradient slabs.
+//
+// Device side: the slab sum shared by gz_reduce_multi (gz_pack.hip) and the fused optimizers that read unreduced
+// weight-gradient slabs directly (gz_optim.hip): ONE definition of the summation order, so that "reduce, then step" and
+// "step from the slabs" give the same bits.  A workgroup of four wavefronts owns 64 float4: wavefront w takes slabs w,
+// w+4, ... of source 0, then of source 1, ... (four independent accumulators per lane), the four partial sums meet in LDS
+// in wavefront order.  The result is valid in wavefront 0.
+//
+// Host side (below): the per-launch slab sums a split weight-gradient launch of gz_conv.hip or gz_conv_direct.hip ends
+// with (kernels in gz_pack.hip), and how gz_conv2d_wgrad_partial / gz_conv2d_wgrad_act_partial ask for them to be left out.
 #pragma once
 #include "gz_common.h"
 
@@ -52,6 +57,26 @@ __device__ __forceinline__ f32x4 reduce_sources(const ReduceSrc* src, int nsrc, 
     __syncthreads();
     if (wave == 0 && live) return ((a0 + part[0][lane]) + part[1][lane]) + part[2][lane];
     return a0;
+}
+
+
+// out[i] = sum_s slab[s][i], i < count (gz_pack.hip: reduce_few_slabs_kernel walks the slabs per thread, reduce_slabs_kernel
+// spreads them over a workgroup; slab rows `stride` floats apart, and the row's tail from `split` on goes to out2 if given)
+void launch_reduce_few_slabs(const float* slab, float* out, int S, long long count, hipStream_t st);
+void launch_reduce_slabs(const float* slab, float* out, int S, long long count, long long stride, float* out2,
+                         long long split, hipStream_t st);
+
+// set by gz_conv2d_wgrad_partial around its dispatch: the split launch reports its slabs instead of reducing them
+struct WgDefer {
+    int nz;
+    long long stride;
+};
+inline thread_local WgDefer* tl_wg_defer = nullptr;
+inline bool defer_reduce(int nz, long long stride) {
+    if (!tl_wg_defer) return false;
+    tl_wg_defer->nz = nz;
+    tl_wg_defer->stride = stride;
+    return true;
 }
 
 }  // namespace gz
