@@ -525,6 +525,22 @@ int gz_rmsprop_step(int count, float* const* params, float* const* grads, float*
                     const long long* numel, float lr, float alpha, float eps, float grad_scale, int zero_grads,
                     hipStream_t stream);
 
+/* ---- generator weight averaging (reference core/submodules/gan_stability/train.py:144-153, update_average) ---------
+ * avg[i] = beta * avg[i] + one_minus_beta * src[i] over ANY number of tensors in one launch: two multiplies and one
+ * add per element without FMA contraction, the same bits on the float4 path (both arrays of a job 16-byte aligned), the
+ * scalar path and under any split of the tensors over launches.  The job table lives in DEVICE memory and is built
+ * once (gz_conv2d_pack_multi's pattern): gz_ema_job fills one host-side record of gz_ema_job_bytes() bytes with the
+ * pair, its element count and first_block = the sum of the block counts returned for the jobs in front of it, and
+ * returns the job's own block count (>= 0; a numel == 0 job has none, is skipped by the launch and may carry null
+ * pointers) or GZ_ERR_BAD_SHAPE for a null pointer, a negative numel / first_block or overlapping avg / src ranges;
+ * it touches no device.  gz_ema_update launches over `count` jobs copied to jobs_dev and total_blocks = the sum of
+ * their block counts (0 launches nothing); beta travels by value, so a captured launch replays.  The caller computes
+ * one_minus_beta as (float)(1.0 - (double)beta), which is what torch makes of the reference's `(1. - beta)`. */
+size_t gz_ema_job_bytes(void);
+int gz_ema_job(void* job_out, float* avg, const float* src, long long numel, int first_block);
+int gz_ema_update(const void* jobs_dev, int count, int total_blocks, float beta, float one_minus_beta,
+                  hipStream_t stream);
+
 /* text of the last HIP error seen by a launcher on the calling thread ("" if none) */
 const char* gz_last_error(void);
 

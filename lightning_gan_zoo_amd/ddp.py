@@ -210,6 +210,8 @@ class GradSync:
         self.measure = bool(os.environ.get("GZ_DDP_MEASURE"))
         self._waits = []              # (optimizer_idx, start event, end event) or (optimizer_idx, seconds)
         self.trace = None             # tests: a list that receives ("issue" | "wait" | "step" | "gate", idx, bucket)
+                                      # and, for a network with a landed callback, ("landed", idx, None)
+        self.on_landed = [None, None]   # per network: called when a pending pass has stepped its LAST bucket
         # the tile / split plans are sized to whole rounds of workgroup slots: with the exchange's channel kernels on the
         # chip, tell the planner how many CUs it can count on (include/gz_ops.h: gz_set_cu_budget)
         self.cu_budget = 256
@@ -421,6 +423,13 @@ class GradSync:
         if self.pending[optimizer_idx] is None:       # (else the flat buffer still holds the pending pass's gradients)
             self.flats[optimizer_idx].flat.zero_()
 
+    def set_landed_callback(self, optimizer_idx, fn):
+        """``fn()`` runs once per optimizer step of network ``optimizer_idx``, right after the LAST bucket of its pending
+        pass has been stepped -- wherever that happens: at a gate of the next forward, in ``finalize`` or in ``flush``.
+        Until then the network is partly stepped; whoever reads all of its weights (weight averaging) reads them from
+        here.  ``None`` removes it."""
+        self.on_landed[optimizer_idx] = fn
+
     # ---- landing a pass ------------------------------------------------------------------------------------------
     def finalize(self, idx, upto=None):
         """Wait for + step the pending buckets of network ``idx`` in issue order: all of them, or up to bucket ``upto``."""
@@ -450,6 +459,10 @@ class GradSync:
             self._step(idx, item.optimizer, fg, item.order[first:stop], reduced)
         if item.done == len(item.order):
             self.pending[idx] = None
+            if self.on_landed[idx] is not None:
+                if self.trace is not None:
+                    self.trace.append(("landed", idx, None))
+                self.on_landed[idx]()
 
     def _step(self, idx, optimizer, fg, buckets, reduced):
         scale = 1.0 / self.world if reduced else 1.0

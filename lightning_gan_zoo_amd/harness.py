@@ -168,10 +168,17 @@ class Trainer:
     count and the ``frequency`` entries as always; the batch's loss is divided by the factor; the optimizer steps (and
     its gradients are cleared) only on batches with ``(batch index in the epoch + 1) % factor == 0`` or on the last
     batch of an epoch -- on every other batch the gradients just accumulate, and under data parallelism nothing is
-    exchanged (Lightning's ``block_ddp_sync_behaviour``): the all-reduce runs on the stepping batch only."""
+    exchanged (Lightning's ``block_ddp_sync_behaviour``): the all-reduce runs on the stepping batch only.
 
-    def __init__(self, module, grad_sync=None, grad_sinks=True, accumulate_grad_batches=1):
+    ``generator_average`` (optional, averaging.GeneratorAverage): advanced once per generator optimizer step, right
+    after it -- under ``grad_sync`` from its "fully landed" callback, i.e. after the pass's last bucket has been
+    stepped, wherever that happens (the next forward's gates, ``finalize``, ``flush``)."""
+
+    def __init__(self, module, grad_sync=None, grad_sinks=True, accumulate_grad_batches=1, generator_average=None):
         self.module = module
+        self.generator_average = generator_average
+        if generator_average is not None and grad_sync is not None:
+            grad_sync.set_landed_callback(1, generator_average.update)
         self.optim = module.configure_optimizers()
         self.order = optimizer_schedule([o["frequency"] for o in self.optim])
         self.grad_sync = grad_sync
@@ -247,6 +254,8 @@ class Trainer:
             else:
                 opt.step()
             opt.zero_grad(set_to_none=True)
+            if idx == 1 and self.generator_average is not None:
+                self.generator_average.update()
         self.batch_idx += 1
         self.epoch_batch_idx += 1
         return loss.detach(), idx
@@ -292,10 +301,10 @@ class GraphedTrainer(Trainer):
     Restrictions (enforced): single process (no GradSync), fused optimizers (Adam with a device-side step counter,
     RMSprop)."""
 
-    def __init__(self, module, warmup=2, grad_sync=None):
+    def __init__(self, module, warmup=2, grad_sync=None, generator_average=None):
         if grad_sync is not None:
             raise RuntimeError("GraphedTrainer is single-process: the data-parallel gradient exchange is not captured")
-        super().__init__(module)
+        super().__init__(module, generator_average=generator_average)
         from . import functional as F
         self._F = F
         self.warmup = warmup
@@ -354,6 +363,8 @@ class GraphedTrainer(Trainer):
         finally:
             self._F.set_grad_sinks(*prev)
         self.optim[idx]["optimizer"].step()
+        if idx == 1 and self.generator_average is not None:
+            self.generator_average.update()       # part of the captured generator body: a replay advances the average
         return loss
 
     def step(self, batch):

@@ -21,6 +21,7 @@ produces them.
 
 The product runner only ever builds the HIP modules on a GPU; tests drive ``fit()`` with their own module / data.
 """
+import contextlib
 import glob
 import math
 import os
@@ -38,8 +39,12 @@ RUNNER_KEYS = {"max_steps": None, "log_every": 10, "dataset_path": None, "seed":
                "inception_weights": None, "inception_check_hash": True, "figures": False,
                # resident training set (resident_data.py): decode once, keep the uint8 set in HBM, one gather launch per
                # batch; data_cache = directory of the decoded-set cache file; a set above resident_max_gb is refused
-               "resident_data": False, "data_cache": None, "resident_max_gb": 32}
+               "resident_data": False, "data_cache": None, "resident_max_gb": 32,
+               # exponential moving average of the generator's weights (averaging.py; gan_stability's update_average with
+               # its model_average_beta default): evaluation, figures and checkpoints see the averaged generator
+               "generator_average": False, "generator_average_beta": 0.999}
 BUILTIN_DATASETS = ("synthetic", "image_folder", "tensor_file", "celeb_a", "mnist")
+AVERAGE_PREFIX = "generator_average."     # state_dict keys of the averaged generator's parameters, next to generator.*
 LIGHTNING_VERSION_TAG = "1.2.0"       # envelope layout written below (Lightning 1.1 / 1.2 generation)
 
 
@@ -367,9 +372,12 @@ def find_ckpt(ckpt_dir):
     return hits[0] if hits else None
 
 
-def checkpoint_blob(module, trainer, step, epoch, keeper=None):
-    """Lightning's checkpoint envelope (``trainer.checkpoint_connector.dump_checkpoint`` of the 1.1 / 1.2 generation)."""
+def checkpoint_blob(module, trainer, step, epoch, keeper=None, average=None):
+    """Lightning's checkpoint envelope (``trainer.checkpoint_connector.dump_checkpoint`` of the 1.1 / 1.2 generation).
+    ``average`` (averaging.GeneratorAverage): its parameters join ``state_dict`` as ``generator_average.<name>``."""
     state = {k: v.detach().cpu() for k, v in module.state_dict().items()}       # generator.* / discriminator.*
+    if average is not None:
+        state.update({AVERAGE_PREFIX + k: v.cpu() for k, v in average.state_dict().items()})
     blob = {"epoch": epoch, "global_step": step, "pytorch-lightning_version": LIGHTNING_VERSION_TAG,
             "state_dict": state,
             "optimizer_states": [o["optimizer"].state_dict() for o in trainer.optim],
@@ -380,18 +388,29 @@ def checkpoint_blob(module, trainer, step, epoch, keeper=None):
     return blob
 
 
-def save_checkpoint(path, module, trainer, step, epoch, keeper=None):
+def save_checkpoint(path, module, trainer, step, epoch, keeper=None, average=None):
     os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
     tmp = path + ".tmp"
-    torch.save(checkpoint_blob(module, trainer, step, epoch, keeper), tmp)
+    torch.save(checkpoint_blob(module, trainer, step, epoch, keeper, average), tmp)
     os.replace(tmp, path)
 
 
-def load_checkpoint(path, module, trainer):
+def load_checkpoint(path, module, trainer, average=None, verbose=True):
+    """``average``: restored from the ``generator_average.*`` entries; a checkpoint without them (an older run, or one
+    with the key off) re-initialises it from the loaded generator and says so (``verbose``)."""
     blob = torch.load(path, map_location="cpu", weights_only=False)
     sd = blob["state_dict"]
     for prefix, net in (("discriminator.", module.discriminator), ("generator.", module.generator)):
         net.load_state_dict({k[len(prefix):]: v for k, v in sd.items() if k.startswith(prefix)})
+    if average is not None:
+        avg = {k[len(AVERAGE_PREFIX):]: v for k, v in sd.items() if k.startswith(AVERAGE_PREFIX)}
+        if avg:
+            average.load_state_dict(avg)
+        else:
+            average.reset()
+            if verbose:
+                print("generator_average: %s holds no averaged weights; the average starts from the loaded generator"
+                      % path)
     for o, s in zip(trainer.optim, blob.get("optimizer_states", [])):
         o["optimizer"].load_state_dict(s)
     for o, s in zip(trainer.optim, blob.get("lr_schedulers", [])):
@@ -452,10 +471,12 @@ class CheckpointKeeper:
 # ---------------------------------------------------------------------------------------------------------
 # the loop
 # ---------------------------------------------------------------------------------------------------------
-def fit(module, cfg, data, run, sync=None, rank=0, world=1, evaluate=None, slow_group=None, figures=None):
+def fit(module, cfg, data, run, sync=None, rank=0, world=1, evaluate=None, slow_group=None, figures=None,
+        average=None):
     """``pl.Trainer(max_epochs=cfg.train.num_epochs, resume_from_checkpoint=find_ckpt(...)).fit(model)`` for the
     step classes of this package (reference run_network.py:61-72).  ``figures``: an EpochFigures, drawn at every epoch
-    end after the FID evaluation.  Returns (module, trainer, global_step)."""
+    end after the FID evaluation.  ``average``: an averaging.GeneratorAverage, advanced after every generator optimizer
+    step, saved in and restored from the checkpoints.  Returns (module, trainer, global_step)."""
     from .harness import Trainer
     t = cfg.train
     # reference run_network.py:61-68: ``1`` or a ``{start_epoch, accumulation_factor}`` node -> Lightning's
@@ -463,7 +484,7 @@ def fit(module, cfg, data, run, sync=None, rank=0, world=1, evaluate=None, slow_
     acc = cfg.get("accumulate_grad_batches", 1)
     if not isinstance(acc, int):
         acc = {int(acc["start_epoch"]): int(acc["accumulation_factor"])}
-    trainer = Trainer(module, grad_sync=sync, accumulate_grad_batches=acc)
+    trainer = Trainer(module, grad_sync=sync, accumulate_grad_batches=acc, generator_average=average)
     n = len(data) if hasattr(data, "__len__") else 0
     steps_per_epoch = int(math.ceil(n / t.batch_size)) if n else int(run["steps_per_epoch"])
     step = epoch = 0
@@ -472,7 +493,7 @@ def fit(module, cfg, data, run, sync=None, rank=0, world=1, evaluate=None, slow_
     keeper = CheckpointKeeper(ckpt_dir) if (ckpt_dir and cfg.get("save_ckpts", True)) else None
     ckpt = find_ckpt(ckpt_dir)
     if ckpt:
-        step, epoch, kst = load_checkpoint(ckpt, module, trainer)
+        step, epoch, kst = load_checkpoint(ckpt, module, trainer, average, verbose=rank == 0)
         trainer.batch_idx = step
         trainer.epoch, trainer.epoch_batch_idx = epoch, step % steps_per_epoch
         if keeper is not None:
@@ -499,7 +520,8 @@ def fit(module, cfg, data, run, sync=None, rank=0, world=1, evaluate=None, slow_
             sync.flush()
             sync.sync_buffers()           # a collective: every rank takes part, rank 0 writes
         if rank == 0:
-            keeper.update(metrics, step, lambda path: save_checkpoint(path, module, trainer, step, epoch, keeper))
+            keeper.update(metrics, step,
+                          lambda path: save_checkpoint(path, module, trainer, step, epoch, keeper, average))
         if world > 1:
             torch.distributed.barrier()
 
@@ -535,6 +557,22 @@ def fit(module, cfg, data, run, sync=None, rank=0, world=1, evaluate=None, slow_
     return module, trainer, step
 
 
+@contextlib.contextmanager
+def rendering_from(module, average):
+    """Inside: ``module.generator`` is the averaged generator (``average.averaged()``: eval mode, the live BatchNorm
+    buffers of this moment); the live generator comes back afterwards.  ``average=None``: nothing changes."""
+    if average is None:
+        yield
+        return
+    live = module.generator
+    module.generator = average.averaged()
+    try:
+        yield
+    finally:
+        module.generator = live
+        average.shadow.eval()         # (a module.train() inside reached the averaged generator, not the live one)
+
+
 class EpochFigures:
     """The reference's figure callbacks at a validation end (core/figures/types.py:78-91, run on_validation_end after
     InceptionMetrics' on_validation_epoch_start has logged this epoch's FID): each figure whose monitor rule passes
@@ -542,10 +580,12 @@ class EpochFigures:
     no_grad and gets its mode back.  HoloGAN's view prefetched for the next step is rolled back first, so that numpy's
     stream reads (figure draws, next step's view) as in the reference.  Every rank makes the same host draws (the
     reference draws on every rank and saves on rank zero); only rank 0 renders and writes.  ``have_fid``: an FID
-    evaluator exists (on rank 0); without one a monitored figure is drawn every epoch, and says so once."""
+    evaluator exists (on rank 0); without one a monitored figure is drawn every epoch, and says so once.  ``average``
+    (averaging.GeneratorAverage): the frames are rendered by the averaged generator; the host draws stay the live one's."""
 
-    def __init__(self, figs, have_fid, rank=0, world=1, group=None):
+    def __init__(self, figs, have_fid, rank=0, world=1, group=None, average=None):
         self.figs, self.have_fid, self.rank, self.world, self.group = list(figs), have_fid, rank, world, group
+        self.average = average
         self._said = False
 
     def score(self, metrics):
@@ -578,7 +618,9 @@ class EpochFigures:
                         continue
                     plan = fig.plan(module)              # host draws: every rank
                     if self.rank == 0:
-                        fig.write(fig.render(module, plan)[1].cpu().numpy(), epoch)
+                        with rendering_from(module, self.average):
+                            frames = fig.render(module, plan)[1]
+                        fig.write(frames.cpu().numpy(), epoch)
         finally:
             module.train(was)
 
@@ -638,7 +680,7 @@ def wants_fid(cfg, run):
                 and str(node.get("_target_", "")).endswith("ImageFolder"))
 
 
-def make_fid_evaluator(cfg, run, module, device):
+def make_fid_evaluator(cfg, run, module, device, average=None):
     """The reference's InceptionMetrics callback (run_network.py:51-56, core/callback_inception_metrics.py:136-246) as
     the ``evaluate`` hook of fit(): FID / KID of ``val.fid_n_samples`` generated images against the validation images,
     both through the InceptionV3 pool features on the HIP kernels (inception.py).  Needs the FID weight file the
@@ -663,7 +705,8 @@ def make_fid_evaluator(cfg, run, module, device):
     real_act = real_activations(val_root, features)
 
     def evaluate(mod, epoch):
-        m = E.evaluate(mod, dump, features, real_act)
+        with rendering_from(mod, average):          # generator_average=true: the averaged generator is what is scored
+            m = E.evaluate(mod, dump, features, real_act)
         print("epoch %d FID: %.4f KID mean: %.6f KID stddev: %.6f" % (epoch, m["fid"], m["kid"], m["kid_std"]))
         return m
 
@@ -696,6 +739,13 @@ def main(argv=None):
         else:
             dist.init_process_group("nccl", device_id=device)
     module = locate(cfg.model.lm["_target_"])(cfg, logging_dir="output").to(device)
+    average = None
+    if run["generator_average"]:
+        from .averaging import GeneratorAverage
+        average = GeneratorAverage(module.generator, beta=float(run["generator_average_beta"]))
+        if rank == 0:
+            print("generator_average: FID / KID and figures render the averaged generator (beta %g); checkpoints hold "
+                  "it as %s*" % (average.beta, AVERAGE_PREFIX))
     slow_group = None
     if world > 1:
         from .ddp import GradSync
@@ -711,7 +761,7 @@ def main(argv=None):
     evaluate, failure = None, None
     if rank == 0:
         try:
-            evaluate = make_fid_evaluator(cfg, run, module, device)
+            evaluate = make_fid_evaluator(cfg, run, module, device, average)
         except BaseException as e:  # noqa: BLE001  (SystemExit from a missing weight file included)
             failure = e
             if slow_group is None:
@@ -734,7 +784,7 @@ def main(argv=None):
         except ValueError as e:
             raise SystemExit("figures: %s" % e) from e
         figures = EpochFigures(figs, have_fid=evaluate is not None or slow_group is not None, rank=rank, world=world,
-                               group=slow_group)
+                               group=slow_group, average=average)
     data_group = slow_group
     if world > 1 and run["resident_data"] and data_group is None:
         # rank 0 decodes the whole training set once while the others wait for its cache file: the same kind of
@@ -743,7 +793,7 @@ def main(argv=None):
         data_group = torch.distributed.new_group(timeout=datetime.timedelta(hours=6), backend="gloo")
     data = build_data(cfg, run, device, rank, world, group=data_group)
     out = fit(module, cfg, data, run, sync=sync, rank=rank, world=world, evaluate=evaluate, slow_group=slow_group,
-              figures=figures)
+              figures=figures, average=average)
     if world > 1:
         torch.distributed.destroy_process_group()
     return out
