@@ -480,7 +480,7 @@ static int run_dgradtap2_impl(const float* y, const float* wp, const float* bias
     const int AH = s.H / G::s, AW = s.W / G::s;
     typename AL::Params pa{y, s, AH, AW, make_fastdiv(AH * AW), make_fastdiv(AW)};
     const int kpad = round_bk(s.K);
-    const int Kt = AL::TY * AL::TX * kpad;
+    const int Kt = AL::Geo::TY * AL::Geo::TX * kpad;
     const int ldc = round4(s.C);
     // (1x1: the plain [K][C] image, without padding rows)
     const int Kb = G::kh * G::kw == 1 ? s.K : Kt;

@@ -233,7 +233,7 @@ static int run_dgradtap3(const float* y, const float* wp, const float* bias, flo
     using Epi = EpiPhase3DB<S>;
     const int AD = s.D / S, AH = s.H / S, AW = s.W / S;
     typename AL::Params pa{y, s, AD, AH, AW, make_fastdiv(AD * AH * AW), make_fastdiv(AH * AW), make_fastdiv(AW)};
-    const int kpad = round_bk(s.K), Kt = AL::T * AL::T * AL::T * kpad, ldc = r4(s.C);
+    const int kpad = round_bk(s.K), Kt = AL::Geo::T * AL::Geo::T * AL::Geo::T * kpad, ldc = r4(s.C);
     typename BL::Params pb{wp, Kt, ldc, ldc, (long long)Kt * ldc};
     const int M = s.N * AD * AH * AW;
     typename Epi::Params pe{x, M, s.C, s.D, s.H, s.W, AD, AH, AW, make_fastdiv(AD * AH * AW), make_fastdiv(AH * AW),

@@ -31,11 +31,11 @@ inline const char* tile_text(TileId t) {
 enum Kind { KUnsupported, KDirect, KIgemm, KIgemm2, KIgemm2w, KIgemm2r, KDg5 };
 enum Loader {
     LGeneric,       // the skeleton's element-wise loaders (ConvFwdALoader / K4V, ConvDgALoader, WgALoader + WgBLoader)
-    LTap,           // igemm: tap-major reduction
+    LTap,           // igemm: tap-major reduction (TapGatherLoader over the form's TapGeo*: Conv*ALoaderTap)
     LRow4,          // igemm: the k4 s2 p1 row loaders (16-byte pieces)
     LWgRow,         // igemm Wg: whole row segments (WgALoaderRow + WgBLoaderRow)
     LRows2,         // igemm2: the geometry's own raw-row loaders (ConvFwdA2 / ConvDgA2)
-    LGather2,       // igemm2: ConvTapA2 / ConvDgTapA2 (conv3d: Conv3DTapA2 / Conv3DDgTapA2)
+    LGather2,       // igemm2: TapGatherA2 over the same geometries: ConvTapA2 / ConvDgTapA2 (conv3d: Conv3DTapA2 / Conv3DDgTapA2)
     LPlane2,        // igemm2: 1x1 as a plain GEMM (PlaneA2)
     LFewk,          // direct 3x3 kernels for <= 4 output channels
     LSmallch,       // direct 3x3 MFMA 16x16x4 kernels

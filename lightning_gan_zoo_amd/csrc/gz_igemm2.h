@@ -167,45 +167,35 @@ struct ConvFwdA2 {
     }
 };
 
-// A operand of a forward convolution of ANY geometry, tap-major reduction (k = (tap, channel), channels padded to a
-// chunk: the layout of ConvFwdALoaderTap and of pack_fwd_tap's weight rows): a chunk is 16 channels at ONE tap, its LDS
-// image [16 channels][BM pixels] a plain gather -- pixel m of channel c sits at x[n][c][S*oy - P + dy][S*ox - P + dx],
-// a fixed per-lane offset plus a per-(channel, tap) scalar.  The elements of a row are S floats apart in memory, so
-// the pieces are 4-BYTE LDS-DMA instructions (64 pixels of one channel each; 16 per wavefront and chunk at BM = 256,
-// three per k-step); taps that fall into the padding are out-of-range lanes (zeros), re-evaluated per lane only when
-// the tap changes (once every C/16 chunks).  Fragment reads are igemm_kernel's plain [k][m] ones: no VALU in the loop.
-template <int BM, int KH, int KW, int S, int P>
-struct ConvTapA2 {
-    static constexpr bool TAPGATHER = true;      // (igemm2_kg2_built: the two-wave-group form is instantiated)
-    using Params = typename ConvFwdALoader<BM, KH, KW, S, P>::Params;
-    static constexpr int LD = BM, ROWS = BK;
+// A operand of every tap-major gather (geometries and the reduction order: gz_igemm_loaders.h, "Tap-major gathers"):
+// a chunk is 16 channels at ONE tap, its LDS image [16 channels][BM pixels] a plain gather -- pixel m of channel c is a
+// fixed per-lane offset (geo.locate) plus a per-(channel, tap) scalar.  The elements of a row are S floats apart in
+// memory (and a transposed phase's rows start anywhere), so the pieces are 4-BYTE LDS-DMA instructions (64 pixels of
+// one channel each; 16 per wavefront and chunk at BM = 256, three per k-step).  Taps that fall into the padding are
+// out-of-range lanes (zeros), re-evaluated per lane only when the tap changes (once every chans/16 chunks), and so are
+// the channels past the end of a padded block.  Fragment reads are igemm_kernel's plain [k][m] ones: no VALU in the loop.
+template <class Geo_>
+struct TapGatherA2 {
+    using Geo = Geo_;
+    using Params = typename Geo::Params;
+    static constexpr int BM = Geo::BM, LD = BM, ROWS = BK;
     static constexpr int G = BM / 64;                      // 64-pixel groups per LDS row
     static constexpr int PIECES = BK * G / 4;              // per wavefront and chunk: its 4 channel rows x G groups
+    Geo geo;
     __amdgpu_buffer_rsrc_t rsrc;
     uint32_t vbase[G], veff[G];
-    int iy0[G], ix0[G];
-    int wave, C, H, W, HW, cblocks, last_tap, last_kc, cb;
+    typename Geo::Pix pix[G];
+    int wave, blocks, last_tap, last_kc, cb;
     uint32_t tap_soff;
     __device__ __forceinline__ void init(const Params& p, int tile, int y, int tid) {
-        const ConvShape& s = p.s;
-        const uint32_t shift = (uint32_t)(P * s.W + P) * 4u;
-        rsrc = make_rsrc(reinterpret_cast<const char*>(p.x) - shift, (uint32_t)s.N * s.C * s.H * s.W * 4u + shift);
+        rsrc = geo.init(p, y);
         const int lane = tid & 63;
         wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-        C = s.C; H = s.H; W = s.W; HW = s.H * s.W;
-        cblocks = round_bk(s.C) / BK;
+        blocks = round_bk(geo.chans) / BK;
         last_tap = -1; last_kc = -1; cb = 0; tap_soff = 0;
 #pragma unroll
         for (int g = 0; g < G; ++g) {
-            const uint32_t m = (uint32_t)tile * BM + g * 64 + lane;
-            const bool m_ok = m < (uint32_t)s.N * s.OH * s.OW;
-            const uint32_t n = fdiv(m, p.div_ohw);
-            const uint32_t pix = m - n * (uint32_t)(s.OH * s.OW);
-            const uint32_t oy = fdiv(pix, p.div_ow);
-            const uint32_t ox = pix - oy * (uint32_t)s.OW;
-            iy0[g] = m_ok ? (int)oy * S - P : -(1 << 20);      // rows past M: every tap out of range
-            ix0[g] = (int)ox * S - P;
-            vbase[g] = (n * (uint32_t)(s.C * HW) + (uint32_t)((iy0[g] + P) * W + (ix0[g] + P))) * 4u;   // shifted base
+            vbase[g] = geo.locate(p, (uint32_t)tile * BM + g * 64 + lane, pix[g]);
             veff[g] = OOB;
         }
     }
@@ -215,162 +205,37 @@ struct ConvTapA2 {
             int tap = last_tap;
             if (kc == last_kc + 1 && last_kc >= 0) {
                 cb += BK;
-                if (cb >= cblocks * BK) { cb = 0; ++tap; }
+                if (cb >= blocks * BK) { cb = 0; ++tap; }
             } else {
-                tap = kc / cblocks;
-                cb = (kc - tap * cblocks) * BK;
+                tap = kc / blocks;
+                cb = (kc - tap * blocks) * BK;
             }
             last_kc = kc;
             if (tap != last_tap) {
                 last_tap = tap;
-                const int dy = tap / KW, dx = tap - dy * KW;
-                tap_soff = (uint32_t)(dy * W + dx) * 4u;
+                const auto tp = geo.tap(tap);
+                tap_soff = geo.tap_bytes(tp);
 #pragma unroll
-                for (int g = 0; g < G; ++g)
-                    veff[g] = ((unsigned)(iy0[g] + dy) < (unsigned)H && (unsigned)(ix0[g] + dx) < (unsigned)W) ? vbase[g] : OOB;
+                for (int g = 0; g < G; ++g) veff[g] = geo.inside(pix[g], tp) ? vbase[g] : OOB;
             }
         }
         const int row = wave * 4 + p / G, g = p % G;
         const int c = cb + row;
         bload_lds4(rsrc, stage + row * LD + g * 64, veff[g],
-                   (live && c < C) ? (uint32_t)c * (uint32_t)HW * 4u + tap_soff : SOFF_OOB);
+                   (live && c < geo.chans) ? (uint32_t)c * (uint32_t)geo.plane * 4u + tap_soff : SOFF_OOB);
     }
 };
 
-// ConvTapA2 with the geometry at RUN time (round 6: the evaluation path's InceptionV3 -- 1x7 / 7x1 / 3x3 / 5x5 / 1x1,
-// strides 1 and 2, asymmetric padding; reference core/submodules/gan_stability/metrics/inception.py): the same chunk =
-// (tap, 16 channels) gather, the same pieces; only the per-tap validity and scalar offset use run-time KW / strides /
-// paddings -- evaluated once per tap, not per chunk.
-template <int BM>
-struct ConvTapAnyA2 {
-    static constexpr bool TAPGATHER = true;
-    using Params = typename ConvFwdALoaderTapAny<BM>::Params;
-    static constexpr int LD = BM, ROWS = BK;
-    static constexpr int G = BM / 64;                      // 64-pixel groups per LDS row
-    static constexpr int PIECES = BK * G / 4;              // per wavefront and chunk: its 4 channel rows x G groups
-    __amdgpu_buffer_rsrc_t rsrc;
-    uint32_t vbase[G], veff[G];
-    int iy0[G], ix0[G];
-    int wave, C, H, W, HW, KW, cblocks, last_tap, last_kc, cb;
-    uint32_t tap_soff;
-    __device__ __forceinline__ void init(const Params& p, int tile, int y, int tid) {
-        const ConvShape& s = p.s;
-        const uint32_t shift = (uint32_t)(p.PH * s.W + p.PW) * 4u;
-        rsrc = make_rsrc(reinterpret_cast<const char*>(p.x) - shift, (uint32_t)s.N * s.C * s.H * s.W * 4u + shift);
-        const int lane = tid & 63;
-        wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-        C = s.C; H = s.H; W = s.W; HW = s.H * s.W; KW = p.KW;
-        cblocks = round_bk(s.C) / BK;
-        last_tap = -1; last_kc = -1; cb = 0; tap_soff = 0;
-#pragma unroll
-        for (int g = 0; g < G; ++g) {
-            const uint32_t m = (uint32_t)tile * BM + g * 64 + lane;
-            const bool m_ok = m < (uint32_t)s.N * s.OH * s.OW;
-            const uint32_t n = fdiv(m, p.div_ohw);
-            const uint32_t pix = m - n * (uint32_t)(s.OH * s.OW);
-            const uint32_t oy = fdiv(pix, p.div_ow);
-            const uint32_t ox = pix - oy * (uint32_t)s.OW;
-            iy0[g] = m_ok ? (int)oy * p.SH - p.PH : -(1 << 20);      // rows past M: every tap out of range
-            ix0[g] = (int)ox * p.SW - p.PW;
-            vbase[g] = (n * (uint32_t)(s.C * HW) + (uint32_t)((iy0[g] + p.PH) * W + (ix0[g] + p.PW))) * 4u;   // shifted base
-            veff[g] = OOB;
-        }
-    }
-    __device__ __forceinline__ void issue_piece(int kc, float* stage, int p, bool live) {
-        if (p == 0) {
-            int tap = last_tap;
-            if (kc == last_kc + 1 && last_kc >= 0) {
-                cb += BK;
-                if (cb >= cblocks * BK) { cb = 0; ++tap; }
-            } else {
-                tap = kc / cblocks;
-                cb = (kc - tap * cblocks) * BK;
-            }
-            last_kc = kc;
-            if (tap != last_tap) {
-                last_tap = tap;
-                const int dy = tap / KW, dx = tap - dy * KW;
-                tap_soff = (uint32_t)(dy * W + dx) * 4u;
-#pragma unroll
-                for (int g = 0; g < G; ++g)
-                    veff[g] = ((unsigned)(iy0[g] + dy) < (unsigned)H && (unsigned)(ix0[g] + dx) < (unsigned)W) ? vbase[g] : OOB;
-            }
-        }
-        const int row = wave * 4 + p / G, g = p % G;
-        const int c = cb + row;
-        bload_lds4(rsrc, stage + row * LD + g * 64, veff[g],
-                   (live && c < C) ? (uint32_t)c * (uint32_t)HW * 4u + tap_soff : SOFF_OOB);
-    }
-};
-
-// The same gather for the TRANSPOSED convolution, phase (py, px), tap-major (ConvDgALoaderTap's reduction order and
-// pack_dgrad_tap's weight rows): chunk = 16 feature channels at one of the phase's ny x nx taps,
-// A[k = (tap, ko)][m = (n, a, b)] = y[n][ko][oy0 - ty][ox0 - tx].  Phases have their own chunk counts.
 template <int BM, int KH, int KW, int S, int P>
-struct ConvDgTapA2 {
-    static constexpr bool TAPGATHER = true;      // (igemm2_kg2_built: the two-wave-group form is instantiated)
-    static constexpr int TY = (KH + S - 1) / S, TX = (KW + S - 1) / S;
-    using Params = typename ConvDgALoaderTap<BM, KH, KW, S, P>::Params;
-    static constexpr int LD = BM, ROWS = BK;
-    static constexpr int G = BM / 64;
-    static constexpr int PIECES = BK * G / 4;
-    __amdgpu_buffer_rsrc_t rsrc;
-    uint32_t vbase[G], veff[G];
-    int oy0[G], ox0[G];
-    int wave, K, OH, OW, OHW, kblocks, nx_p, last_tap, last_kc, kob;
-    uint32_t tap_soff;
-    __device__ __forceinline__ void init(const Params& p, int tile, int phase, int tid) {
-        const ConvShape& s = p.s;
-        const uint32_t shift = (uint32_t)((TY - 1) * s.OW + (TX - 1)) * 4u;
-        rsrc = make_rsrc(reinterpret_cast<const char*>(p.y) - shift, (uint32_t)s.N * s.K * s.OH * s.OW * 4u + shift);
-        const int lane = tid & 63;
-        wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-        const int py = phase / S, px = phase % S;
-        nx_p = dg_taps(KW, S, P, px);
-        K = s.K; OH = s.OH; OW = s.OW; OHW = s.OH * s.OW;
-        kblocks = round_bk(s.K) / BK;
-        last_tap = -1; last_kc = -1; kob = 0; tap_soff = 0;
-#pragma unroll
-        for (int g = 0; g < G; ++g) {
-            const uint32_t m = (uint32_t)tile * BM + g * 64 + lane;
-            const bool m_ok = m < (uint32_t)s.N * p.AH * p.AW;
-            const uint32_t n = fdiv(m, p.div_ahw);
-            const uint32_t pix = m - n * (uint32_t)(p.AH * p.AW);
-            const uint32_t a = fdiv(pix, p.div_aw);
-            const uint32_t b = pix - a * (uint32_t)p.AW;
-            oy0[g] = m_ok ? (int)a + (py + P) / S : -(1 << 20);
-            ox0[g] = (int)b + (px + P) / S;
-            // addresses (oy0 - (TY-1), ox0 - (TX-1)) through the shifted base; the tap's scalar offset walks forward
-            vbase[g] = (n * (uint32_t)(s.K * OHW) + (uint32_t)(((int)a + (py + P) / S) * OW + ox0[g])) * 4u;
-            veff[g] = OOB;
-        }
-    }
-    __device__ __forceinline__ void issue_piece(int kc, float* stage, int p, bool live) {
-        if (p == 0) {
-            int tap = last_tap;
-            if (kc == last_kc + 1 && last_kc >= 0) {
-                kob += BK;
-                if (kob >= kblocks * BK) { kob = 0; ++tap; }
-            } else {
-                tap = kc / kblocks;
-                kob = (kc - tap * kblocks) * BK;
-            }
-            last_kc = kc;
-            if (tap != last_tap) {
-                last_tap = tap;
-                const int ty = tap / nx_p, tx = tap - ty * nx_p;
-                tap_soff = (uint32_t)((TY - 1 - ty) * OW + (TX - 1 - tx)) * 4u;
-#pragma unroll
-                for (int g = 0; g < G; ++g)
-                    veff[g] = ((unsigned)(oy0[g] - ty) < (unsigned)OH && (unsigned)(ox0[g] - tx) < (unsigned)OW) ? vbase[g] : OOB;
-            }
-        }
-        const int row = wave * 4 + p / G, g = p % G;
-        const int ko = kob + row;
-        bload_lds4(rsrc, stage + row * LD + g * 64, veff[g],
-                   (live && ko < K) ? (uint32_t)ko * (uint32_t)OHW * 4u + tap_soff : SOFF_OOB);
-    }
-};
+using ConvTapA2 = TapGatherA2<TapGeoFwd<BM, KH, KW, S, P>>;
+template <int BM>
+using ConvTapAnyA2 = TapGatherA2<TapGeoFwdAny<BM>>;
+template <int BM, int KH, int KW, int S, int P>
+using ConvDgTapA2 = TapGatherA2<TapGeoDg<BM, KH, KW, S, P>>;
+template <int BM, int KS, int S, int P>
+using Conv3DTapA2 = TapGatherA2<TapGeoFwd3D<BM, KS, S, P>>;
+template <int BM, int KS, int S, int P>
+using Conv3DDgTapA2 = TapGatherA2<TapGeoDg3D<BM, KS, S, P>>;
 
 // ---- round 6: the 5x5 s2 p2 TRANSPOSED convolution, row-shared (HoloGAN's critic, input gradients) -------------------
 // ConvDgTapA2 above gathers a chunk per (tap, 16 channels): the 9 / 6 / 6 / 4 taps of the four output phases each fetch
@@ -533,150 +398,6 @@ struct PlaneA2 {
         const int row = wave * 4 + p / PPR, g = p % PPR;
         const int c = kc * BK + row;
         bload_lds16(rsrc, stage + row * LD + g * 256, voff[g], (live && c < CH) ? (uint32_t)c * plane : SOFF_OOB);
-    }
-};
-
-// The two gathers in three dimensions (HoloGAN's ConvTranspose3d k3 s2 p1 op1, core/models/hologan_generator.py:29-30:
-// its forward is the transposed form with 8 phases of 1..8 taps, its input gradient the plain strided convolution).
-// Tap-major: chunk = 16 channels at one tap; the weight rows follow pack_fwd3_tap / pack_dgrad3_tap (gz_conv3d.hip).
-template <int BM, int KS, int S, int P>
-struct Conv3DTapA2 {
-    using Params = typename Conv3DFwdALoader<BM, KS, S, P>::Params;
-    static constexpr int LD = BM, ROWS = BK;
-    static constexpr int G = BM / 64;
-    static constexpr int PIECES = BK * G / 4;
-    __amdgpu_buffer_rsrc_t rsrc;
-    uint32_t vbase[G], veff[G];
-    int id0[G], iy0[G], ix0[G];
-    int wave, C, D, H, W, DHW, cblocks, last_tap, last_kc, cb;
-    uint32_t tap_soff;
-    __device__ __forceinline__ void init(const Params& p, int tile, int y, int tid) {
-        const Conv3DShape& s = p.s;
-        const uint32_t shift = (uint32_t)((P * s.H + P) * s.W + P) * 4u;
-        rsrc = make_rsrc(reinterpret_cast<const char*>(p.x) - shift,
-                         (uint32_t)s.N * s.C * s.D * s.H * s.W * 4u + shift);
-        const int lane = tid & 63;
-        wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-        C = s.C; D = s.D; H = s.H; W = s.W; DHW = s.D * s.H * s.W;
-        cblocks = round_bk(s.C) / BK;
-        last_tap = -1; last_kc = -1; cb = 0; tap_soff = 0;
-#pragma unroll
-        for (int g = 0; g < G; ++g) {
-            const uint32_t m = (uint32_t)tile * BM + g * 64 + lane;
-            const bool m_ok = m < (uint32_t)s.N * s.OD * s.OH * s.OW;
-            const uint32_t n = fdiv(m, p.div_odhw);
-            uint32_t v = m - n * (uint32_t)(s.OD * s.OH * s.OW);
-            const uint32_t od = fdiv(v, p.div_ohw);
-            v -= od * (uint32_t)(s.OH * s.OW);
-            const uint32_t oy = fdiv(v, p.div_ow);
-            const uint32_t ox = v - oy * (uint32_t)s.OW;
-            id0[g] = m_ok ? (int)od * S - P : -(1 << 20);      // rows past M: every tap out of range
-            iy0[g] = (int)oy * S - P;
-            ix0[g] = (int)ox * S - P;
-            vbase[g] = (n * (uint32_t)(s.C * DHW) +
-                        (uint32_t)((((int)od * S) * H + (iy0[g] + P)) * W + (ix0[g] + P))) * 4u;   // shifted base
-            veff[g] = OOB;
-        }
-    }
-    __device__ __forceinline__ void issue_piece(int kc, float* stage, int p, bool live) {
-        if (p == 0) {
-            int tap = last_tap;
-            if (kc == last_kc + 1 && last_kc >= 0) {
-                cb += BK;
-                if (cb >= cblocks * BK) { cb = 0; ++tap; }
-            } else {
-                tap = kc / cblocks;
-                cb = (kc - tap * cblocks) * BK;
-            }
-            last_kc = kc;
-            if (tap != last_tap) {
-                last_tap = tap;
-                const int kd = tap / (KS * KS), r = tap - kd * (KS * KS), ky = r / KS, kx = r - ky * KS;
-                tap_soff = (uint32_t)((kd * H + ky) * W + kx) * 4u;
-#pragma unroll
-                for (int g = 0; g < G; ++g)
-                    veff[g] = ((unsigned)(id0[g] + kd) < (unsigned)D && (unsigned)(iy0[g] + ky) < (unsigned)H &&
-                               (unsigned)(ix0[g] + kx) < (unsigned)W) ? vbase[g] : OOB;
-            }
-        }
-        const int row = wave * 4 + p / G, g = p % G;
-        const int c = cb + row;
-        bload_lds4(rsrc, stage + row * LD + g * 64, veff[g],
-                   (live && c < C) ? (uint32_t)c * (uint32_t)DHW * 4u + tap_soff : SOFF_OOB);
-    }
-};
-
-// A[k = (tap, ko)][m = (n, a, b, c)] = y[n][ko][od0 - td][oy0 - ty][ox0 - tx] of phase (pd, py, px); a phase has its own
-// nd x ny x nx taps (tap = (td * ny + ty) * nx + tx) and chunk count.
-template <int BM, int KS, int S, int P>
-struct Conv3DDgTapA2 {
-    static constexpr int T = (KS + S - 1) / S;
-    using Params = typename Conv3DDgALoader<BM, KS, S, P>::Params;
-    static constexpr int LD = BM, ROWS = BK;
-    static constexpr int G = BM / 64;
-    static constexpr int PIECES = BK * G / 4;
-    __amdgpu_buffer_rsrc_t rsrc;
-    uint32_t vbase[G], veff[G];
-    int od0[G], oy0[G], ox0[G];
-    int wave, K, OD, OH, OW, OSP, kblocks, ny_p, nx_p, last_tap, last_kc, kob;
-    uint32_t tap_soff;
-    __device__ __forceinline__ void init(const Params& p, int tile, int phase, int tid) {
-        const Conv3DShape& s = p.s;
-        const uint32_t shift = (uint32_t)(((T - 1) * s.OH + (T - 1)) * s.OW + (T - 1)) * 4u;
-        rsrc = make_rsrc(reinterpret_cast<const char*>(p.y) - shift,
-                         (uint32_t)s.N * s.K * s.OD * s.OH * s.OW * 4u + shift);
-        const int lane = tid & 63;
-        wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-        const int pd = phase / (S * S), py = (phase / S) % S, px = phase % S;
-        ny_p = dg_taps(KS, S, P, py);
-        nx_p = dg_taps(KS, S, P, px);
-        K = s.K; OD = s.OD; OH = s.OH; OW = s.OW; OSP = s.OD * s.OH * s.OW;
-        kblocks = round_bk(s.K) / BK;
-        last_tap = -1; last_kc = -1; kob = 0; tap_soff = 0;
-#pragma unroll
-        for (int g = 0; g < G; ++g) {
-            const uint32_t m = (uint32_t)tile * BM + g * 64 + lane;
-            const bool m_ok = m < (uint32_t)s.N * p.AD * p.AH * p.AW;
-            const uint32_t n = fdiv(m, p.div_adhw);
-            uint32_t v = m - n * (uint32_t)(p.AD * p.AH * p.AW);
-            const uint32_t a = fdiv(v, p.div_ahw);
-            v -= a * (uint32_t)(p.AH * p.AW);
-            const uint32_t b = fdiv(v, p.div_aw);
-            const uint32_t c = v - b * (uint32_t)p.AW;
-            const int od = (int)a + (pd + P) / S;
-            od0[g] = m_ok ? od : -(1 << 20);
-            oy0[g] = (int)b + (py + P) / S;
-            ox0[g] = (int)c + (px + P) / S;
-            // addresses (od - (T-1), oy0 - (T-1), ox0 - (T-1)) through the shifted base; the tap's scalar offset walks forward
-            vbase[g] = (n * (uint32_t)(s.K * OSP) + (uint32_t)((od * OH + oy0[g]) * OW + ox0[g])) * 4u;
-            veff[g] = OOB;
-        }
-    }
-    __device__ __forceinline__ void issue_piece(int kc, float* stage, int p, bool live) {
-        if (p == 0) {
-            int tap = last_tap;
-            if (kc == last_kc + 1 && last_kc >= 0) {
-                kob += BK;
-                if (kob >= kblocks * BK) { kob = 0; ++tap; }
-            } else {
-                tap = kc / kblocks;
-                kob = (kc - tap * kblocks) * BK;
-            }
-            last_kc = kc;
-            if (tap != last_tap) {
-                last_tap = tap;
-                const int td = tap / (ny_p * nx_p), r = tap - td * (ny_p * nx_p), ty = r / nx_p, tx = r - ty * nx_p;
-                tap_soff = (uint32_t)(((T - 1 - td) * OH + (T - 1 - ty)) * OW + (T - 1 - tx)) * 4u;
-#pragma unroll
-                for (int g = 0; g < G; ++g)
-                    veff[g] = ((unsigned)(od0[g] - td) < (unsigned)OD && (unsigned)(oy0[g] - ty) < (unsigned)OH &&
-                               (unsigned)(ox0[g] - tx) < (unsigned)OW) ? vbase[g] : OOB;
-            }
-        }
-        const int row = wave * 4 + p / G, g = p % G;
-        const int ko = kob + row;
-        bload_lds4(rsrc, stage + row * LD + g * 64, veff[g],
-                   (live && ko < K) ? (uint32_t)ko * (uint32_t)OSP * 4u + tap_soff : SOFF_OOB);
     }
 };
 
@@ -1742,7 +1463,7 @@ constexpr size_t igemm2_lds_bytes_kg2() {
 template <class T, class = void>
 struct is_tapgather : std::false_type {};
 template <class T>
-struct is_tapgather<T, std::void_t<decltype(T::TAPGATHER)>> : std::true_type {};
+struct is_tapgather<T, std::void_t<decltype(T::Geo::TAPGATHER)>> : std::true_type {};      // (a property of the geometry)
 template <class Cfg, class AL>
 constexpr bool igemm2_kg2_built() {
     return Cfg::TN <= 2 && Cfg::WM * Cfg::WN == 4 && Cfg::WN == 2 && !is_dualmode<AL>::value &&

@@ -299,235 +299,6 @@ struct ConvFwdALoader {
     }
 };
 
-// Tap-major reduction order for kernels whose tap count does not divide a chunk (3x3: 9, 5x5: 25): with the
-// usual k = (c, tap) order every element of every chunk needs its own (c, ky, kx) decode and bounds test -- ~25
-// VALU instructions per 4-byte load, which made the 16-channel 128x128 ResNet layers VALU-bound on address
-// arithmetic.  With k = (tap, c), c padded to a multiple of BK, a chunk is ONE tap and BK consecutive channels:
-// per lane the voffsets are loop-invariant (pixel + its BK/STEP channel rows), the tap and the channel block
-// advance through the wave-uniform scalar offset, and the padding test is one compare pair per chunk.
-// The descriptor base is moved back by the largest negative tap shift so that voffsets stay non-negative; taps
-// in the padding use the out-of-range voffset and are never dereferenced.
-
-// A[m = (n, oy, ox)][k = (tap, c)] = x[n][c][oy*S-P+ky][ox*S-P+kx]
-template <int BM, int KH, int KW, int S, int P>
-struct ConvFwdALoaderTap {
-    using Params = typename ConvFwdALoader<BM, KH, KW, S, P>::Params;
-    static constexpr int LD = BM;
-    static constexpr int EPT = BM * BK / NT;
-    static constexpr int STEP = NT / BM;
-    static constexpr bool DMA = GZ_IGEMM_DMA;
-    static constexpr int NPARTS = 0;
-    __device__ __forceinline__ void issue_lds_part(int, float*, int) {}
-    __amdgpu_buffer_rsrc_t rsrc;
-    uint32_t voff[EPT];
-    int kb, m_l, iy0, ix0, C, H, W, cblocks;
-    bool m_ok;
-    float r[DMA ? 1 : EPT];
-    __device__ __forceinline__ void init(const Params& p, int tile, int y, int tid) {
-        const ConvShape& s = p.s;
-        const uint32_t shift = (uint32_t)(P * s.W + P) * 4u;
-        rsrc = make_rsrc(reinterpret_cast<const char*>(p.x) - shift, (uint32_t)s.N * s.C * s.H * s.W * 4u + shift);
-        m_l = tid % BM;
-        kb = tid / BM;
-        uint32_t m = (uint32_t)tile * BM + m_l;
-        m_ok = m < (uint32_t)s.N * s.OH * s.OW;
-        uint32_t n = fdiv(m, p.div_ohw);
-        uint32_t pix = m - n * (uint32_t)(s.OH * s.OW);
-        uint32_t oy = fdiv(pix, p.div_ow);
-        uint32_t ox = pix - oy * (uint32_t)s.OW;
-        iy0 = (int)oy * S - P;
-        ix0 = (int)ox * S - P;
-        C = s.C; H = s.H; W = s.W;
-        cblocks = round_bk(s.C) / BK;
-        const int pos = (int)(n * (uint32_t)(s.C * s.H * s.W)) + (iy0 + P) * W + (ix0 + P);   // >= 0 (shifted base)
-#pragma unroll
-        for (int j = 0; j < EPT; ++j) voff[j] = (uint32_t)(pos + (kb + STEP * j) * H * W) * 4u;
-    }
-    // chunk -> (tap, channel block): wave-uniform
-    __device__ __forceinline__ void chunk(int kc, uint32_t& soff, bool& ok, int& cb) const {
-        const int tap = kc / cblocks;
-        cb = (kc - tap * cblocks) * BK;
-        const int dy = tap / KW, dx = tap - dy * KW;
-        soff = (uint32_t)(cb * H * W + dy * W + dx) * 4u;
-        ok = m_ok && (unsigned)(iy0 + dy) < (unsigned)H && (unsigned)(ix0 + dx) < (unsigned)W;
-    }
-    __device__ __forceinline__ void issue_lds(int kc, float* dst) {
-        float* wbase = dst + (m_l - (int)(threadIdx.x & 63));
-        uint32_t soff; bool ok; int cb;
-        chunk(kc, soff, ok, cb);
-#pragma unroll
-        for (int j = 0; j < EPT; ++j)
-            bload_lds4(rsrc, wbase + (kb + STEP * j) * LD, (ok && cb + kb + STEP * j < C) ? voff[j] : OOB, soff);
-    }
-    __device__ __forceinline__ void issue(int kc) {
-        if constexpr (!DMA) {
-            uint32_t soff; bool ok; int cb;
-            chunk(kc, soff, ok, cb);
-#pragma unroll
-            for (int j = 0; j < EPT; ++j) r[j] = bload(rsrc, (ok && cb + kb + STEP * j < C) ? voff[j] : OOB, soff);
-        }
-    }
-    __device__ __forceinline__ void commit(float* dst) const {
-        if constexpr (!DMA) {
-#pragma unroll
-            for (int j = 0; j < EPT; ++j) dst[(kb + STEP * j) * LD + m_l] = r[j];
-        }
-    }
-};
-
-// The same tap-major forward loader with the geometry as run-time values (rectangular kernels, per-axis stride and
-// padding): the evaluation path's InceptionV3 has 3x3 s2 p0, 5x5 s1 p2, 1x7 / 7x1, 1x3 / 3x1 ... layers, none of
-// which is worth a template instantiation of its own (forward only, no training step runs through them).
-template <int BM>
-struct ConvFwdALoaderTapAny {
-    struct Params {
-        const float* x;
-        ConvShape s;
-        FastDiv div_ohw, div_ow;
-        int KH, KW, SH, SW, PH, PW;
-    };
-    static constexpr int LD = BM;
-    static constexpr int EPT = BM * BK / NT;
-    static constexpr int STEP = NT / BM;
-    static constexpr bool DMA = GZ_IGEMM_DMA;
-    static constexpr int NPARTS = 0;
-    __device__ __forceinline__ void issue_lds_part(int, float*, int) {}
-    __amdgpu_buffer_rsrc_t rsrc;
-    uint32_t voff[EPT];
-    int kb, m_l, iy0, ix0, C, H, W, cblocks, KW;
-    bool m_ok;
-    float r[DMA ? 1 : EPT];
-    __device__ __forceinline__ void init(const Params& p, int tile, int y, int tid) {
-        const ConvShape& s = p.s;
-        const uint32_t shift = (uint32_t)(p.PH * s.W + p.PW) * 4u;
-        rsrc = make_rsrc(reinterpret_cast<const char*>(p.x) - shift, (uint32_t)s.N * s.C * s.H * s.W * 4u + shift);
-        m_l = tid % BM;
-        kb = tid / BM;
-        uint32_t m = (uint32_t)tile * BM + m_l;
-        m_ok = m < (uint32_t)s.N * s.OH * s.OW;
-        uint32_t n = fdiv(m, p.div_ohw);
-        uint32_t pix = m - n * (uint32_t)(s.OH * s.OW);
-        uint32_t oy = fdiv(pix, p.div_ow);
-        uint32_t ox = pix - oy * (uint32_t)s.OW;
-        iy0 = (int)oy * p.SH - p.PH;
-        ix0 = (int)ox * p.SW - p.PW;
-        C = s.C; H = s.H; W = s.W; KW = p.KW;
-        cblocks = round_bk(s.C) / BK;
-        const int pos = (int)(n * (uint32_t)(s.C * s.H * s.W)) + (iy0 + p.PH) * W + (ix0 + p.PW);   // >= 0 (shifted base)
-#pragma unroll
-        for (int j = 0; j < EPT; ++j) voff[j] = (uint32_t)(pos + (kb + STEP * j) * H * W) * 4u;
-    }
-    __device__ __forceinline__ void chunk(int kc, uint32_t& soff, bool& ok, int& cb) const {
-        const int tap = kc / cblocks;
-        cb = (kc - tap * cblocks) * BK;
-        const int dy = tap / KW, dx = tap - dy * KW;
-        soff = (uint32_t)(cb * H * W + dy * W + dx) * 4u;
-        ok = m_ok && (unsigned)(iy0 + dy) < (unsigned)H && (unsigned)(ix0 + dx) < (unsigned)W;
-    }
-    __device__ __forceinline__ void issue_lds(int kc, float* dst) {
-        float* wbase = dst + (m_l - (int)(threadIdx.x & 63));
-        uint32_t soff; bool ok; int cb;
-        chunk(kc, soff, ok, cb);
-#pragma unroll
-        for (int j = 0; j < EPT; ++j)
-            bload_lds4(rsrc, wbase + (kb + STEP * j) * LD, (ok && cb + kb + STEP * j < C) ? voff[j] : OOB, soff);
-    }
-    __device__ __forceinline__ void issue(int kc) {
-        if constexpr (!DMA) {
-            uint32_t soff; bool ok; int cb;
-            chunk(kc, soff, ok, cb);
-#pragma unroll
-            for (int j = 0; j < EPT; ++j) r[j] = bload(rsrc, (ok && cb + kb + STEP * j < C) ? voff[j] : OOB, soff);
-        }
-    }
-    __device__ __forceinline__ void commit(float* dst) const {
-        if constexpr (!DMA) {
-#pragma unroll
-            for (int j = 0; j < EPT; ++j) dst[(kb + STEP * j) * LD + m_l] = r[j];
-        }
-    }
-};
-
-// transposed conv, phase (py, px), tap-major: A[m = (n, a, b)][k = (tap, ko)] = y[n][ko][oy0 - ty][ox0 - tx] with
-// tap = ty * nx + tx over the phase's own ny x nx taps (dg_taps); the weight rows of a phase are packed in the
-// same order (pack_dgrad_tap_kernel), so phases with fewer taps simply have fewer chunks.
-template <int BM, int KH, int KW, int S, int P>
-struct ConvDgALoaderTap {
-    static constexpr int TY = (KH + S - 1) / S, TX = (KW + S - 1) / S;
-    static constexpr int TAPS = TY * TX;
-    static constexpr bool UNIFORM = false;      // phases have their own chunk counts (run_dgrad passes them)
-    struct Params {
-        const float* y;
-        ConvShape s;
-        int AH, AW;
-        FastDiv div_ahw, div_aw;
-    };
-    static constexpr int LD = BM;
-    static constexpr int EPT = BM * BK / NT;
-    static constexpr int STEP = NT / BM;
-    static constexpr bool DMA = GZ_IGEMM_DMA;
-    static constexpr int NPARTS = 0;
-    __device__ __forceinline__ void issue_lds_part(int, float*, int) {}
-    __amdgpu_buffer_rsrc_t rsrc;
-    uint32_t voff[EPT];
-    int kb, m_l, oy0, ox0, K, OH, OW, kblocks, nx_p;
-    bool m_ok;
-    float r[DMA ? 1 : EPT];
-    __device__ __forceinline__ void init(const Params& p, int tile, int phase, int tid) {
-        const ConvShape& s = p.s;
-        const uint32_t shift = (uint32_t)((TY - 1) * s.OW + (TX - 1)) * 4u;
-        rsrc = make_rsrc(reinterpret_cast<const char*>(p.y) - shift, (uint32_t)s.N * s.K * s.OH * s.OW * 4u + shift);
-        m_l = tid % BM;
-        kb = tid / BM;
-        const int py = phase / S, px = phase % S;
-        nx_p = dg_taps(KW, S, P, px);
-        uint32_t m = (uint32_t)tile * BM + m_l;
-        m_ok = m < (uint32_t)s.N * p.AH * p.AW;
-        uint32_t n = fdiv(m, p.div_ahw);
-        uint32_t pix = m - n * (uint32_t)(p.AH * p.AW);
-        uint32_t a = fdiv(pix, p.div_aw);
-        uint32_t b = pix - a * (uint32_t)p.AW;
-        oy0 = (int)a + (py + P) / S;
-        ox0 = (int)b + (px + P) / S;
-        K = s.K; OH = s.OH; OW = s.OW;
-        kblocks = round_bk(s.K) / BK;
-        // voffsets address (oy0 - (TY-1), ox0 - (TX-1)) through the shifted base; the chunk's scalar offset
-        // walks forward from there to (oy0 - ty, ox0 - tx)
-        const int pos = (int)(n * (uint32_t)(s.K * s.OH * s.OW)) + oy0 * OW + ox0;
-#pragma unroll
-        for (int j = 0; j < EPT; ++j) voff[j] = (uint32_t)(pos + (kb + STEP * j) * OH * OW) * 4u;
-    }
-    __device__ __forceinline__ void chunk(int kc, uint32_t& soff, bool& ok, int& kob) const {
-        const int tap = kc / kblocks;
-        kob = (kc - tap * kblocks) * BK;
-        const int ty = tap / nx_p, tx = tap - ty * nx_p;
-        soff = (uint32_t)(kob * OH * OW + (TY - 1 - ty) * OW + (TX - 1 - tx)) * 4u;
-        ok = m_ok && (unsigned)(oy0 - ty) < (unsigned)OH && (unsigned)(ox0 - tx) < (unsigned)OW;
-    }
-    __device__ __forceinline__ void issue_lds(int kc, float* dst) {
-        float* wbase = dst + (m_l - (int)(threadIdx.x & 63));
-        uint32_t soff; bool ok; int kob;
-        chunk(kc, soff, ok, kob);
-#pragma unroll
-        for (int j = 0; j < EPT; ++j)
-            bload_lds4(rsrc, wbase + (kb + STEP * j) * LD, (ok && kob + kb + STEP * j < K) ? voff[j] : OOB, soff);
-    }
-    __device__ __forceinline__ void issue(int kc) {
-        if constexpr (!DMA) {
-            uint32_t soff; bool ok; int kob;
-            chunk(kc, soff, ok, kob);
-#pragma unroll
-            for (int j = 0; j < EPT; ++j) r[j] = bload(rsrc, (ok && kob + kb + STEP * j < K) ? voff[j] : OOB, soff);
-        }
-    }
-    __device__ __forceinline__ void commit(float* dst) const {
-        if constexpr (!DMA) {
-#pragma unroll
-            for (int j = 0; j < EPT; ++j) dst[(kb + STEP * j) * LD + m_l] = r[j];
-        }
-    }
-};
-
 // Forward loader for KW == 4, KH*KW == 16 (the k4 s2 p1 layers): the four kx taps of one (c, ky) are four
 // consecutive floats of an input row, so each lane gathers them with ONE 16-byte load (dword aligned)
 // instead of four 4-byte loads -- a chunk (one input channel) needs 2 vector loads per lane instead of 8.
@@ -1136,75 +907,6 @@ struct Conv3DFwdALoader {
     }
 };
 
-// tap-major variant (see ConvFwdALoaderTap): A[m = (n, od, oy, ox)][k = (tap, c)], c padded to a multiple of BK
-template <int BM, int KS, int S, int P>
-struct Conv3DFwdALoaderTap {
-    using Params = typename Conv3DFwdALoader<BM, KS, S, P>::Params;
-    static constexpr int LD = BM;
-    static constexpr int NPARTS = 0;
-    __device__ __forceinline__ void issue_lds_part(int, float*, int) {}
-    static constexpr bool DMA = GZ_IGEMM_DMA;
-    static constexpr int EPT = BM * BK / NT;
-    static constexpr int STEP = NT / BM;
-    __amdgpu_buffer_rsrc_t rsrc;
-    uint32_t voff[EPT];
-    int kb, m_l, id0, iy0, ix0, C, D, H, W, cblocks;
-    bool m_ok;
-    float r[DMA ? 1 : EPT];
-    __device__ __forceinline__ void init(const Params& p, int tile, int y, int tid) {
-        const Conv3DShape& s = p.s;
-        const uint32_t shift = (uint32_t)((P * s.H + P) * s.W + P) * 4u;
-        rsrc = make_rsrc(reinterpret_cast<const char*>(p.x) - shift,
-                         (uint32_t)s.N * s.C * s.D * s.H * s.W * 4u + shift);
-        m_l = tid % BM;
-        kb = tid / BM;
-        uint32_t m = (uint32_t)tile * BM + m_l;
-        m_ok = m < (uint32_t)s.N * s.OD * s.OH * s.OW;
-        uint32_t n = fdiv(m, p.div_odhw);
-        uint32_t v = m - n * (uint32_t)(s.OD * s.OH * s.OW);
-        uint32_t od = fdiv(v, p.div_ohw);
-        v -= od * (uint32_t)(s.OH * s.OW);
-        uint32_t oy = fdiv(v, p.div_ow);
-        uint32_t ox = v - oy * (uint32_t)s.OW;
-        id0 = (int)od * S - P; iy0 = (int)oy * S - P; ix0 = (int)ox * S - P;
-        C = s.C; D = s.D; H = s.H; W = s.W;
-        cblocks = round_bk(s.C) / BK;
-        const int pos = (int)(n * (uint32_t)(s.C * s.D * s.H * s.W)) + ((id0 + P) * H + (iy0 + P)) * W + (ix0 + P);
-#pragma unroll
-        for (int j = 0; j < EPT; ++j) voff[j] = (uint32_t)(pos + (kb + STEP * j) * D * H * W) * 4u;
-    }
-    __device__ __forceinline__ void chunk(int kc, uint32_t& soff, bool& ok, int& cb) const {
-        const int tap = kc / cblocks;
-        cb = (kc - tap * cblocks) * BK;
-        const int kd = tap / (KS * KS), ky = (tap / KS) % KS, kx = tap % KS;
-        soff = (uint32_t)(cb * D * H * W + (kd * H + ky) * W + kx) * 4u;
-        ok = m_ok && (unsigned)(id0 + kd) < (unsigned)D && (unsigned)(iy0 + ky) < (unsigned)H &&
-             (unsigned)(ix0 + kx) < (unsigned)W;
-    }
-    __device__ __forceinline__ void issue_lds(int kc, float* dst) {
-        float* wbase = dst + (m_l - (int)(threadIdx.x & 63));
-        uint32_t soff; bool ok; int cb;
-        chunk(kc, soff, ok, cb);
-#pragma unroll
-        for (int j = 0; j < EPT; ++j)
-            bload_lds4(rsrc, wbase + (kb + STEP * j) * LD, (ok && cb + kb + STEP * j < C) ? voff[j] : OOB, soff);
-    }
-    __device__ __forceinline__ void issue(int kc) {
-        if constexpr (!DMA) {
-            uint32_t soff; bool ok; int cb;
-            chunk(kc, soff, ok, cb);
-#pragma unroll
-            for (int j = 0; j < EPT; ++j) r[j] = bload(rsrc, (ok && cb + kb + STEP * j < C) ? voff[j] : OOB, soff);
-        }
-    }
-    __device__ __forceinline__ void commit(float* dst) const {
-        if constexpr (!DMA) {
-#pragma unroll
-            for (int j = 0; j < EPT; ++j) dst[(kb + STEP * j) * LD + m_l] = r[j];
-        }
-    }
-};
-
 // transposed 3-D conv, phase (pd, py, px): A[m = (n, a, b, c)][k = (ko, td, ty, tx)]
 template <int BM, int KS, int S, int P>
 struct Conv3DDgALoader {
@@ -1353,5 +1055,302 @@ struct Wg3DBLoader {
         for (int j = 0; j < EPT; ++j) dst[kl * LD + n_l + 16 * j] = r[j];
     }
 };
+
+// ---------------------------------------------------------------------------
+// Tap-major gathers: one geometry per convolution form, one staging body per skeleton.
+//
+// Why tap-major.  For kernels whose tap count does not divide a chunk (3x3: 9, 5x5: 25) the usual k = (c, tap)
+// order needs a (c, ky, kx) decode and bounds test for every element of every chunk -- ~25 VALU instructions per
+// 4-byte load, which made the 16-channel 128x128 ResNet layers VALU-bound on address arithmetic.  With k = (tap, c),
+// c padded to a multiple of BK (the weight rows of pack_fwd_tap / pack_dgrad_tap and their 3-D twins), a chunk is
+// ONE tap and BK consecutive channels: per lane the voffset is loop-invariant (its pixel), the tap and the channel
+// block advance through the wave-uniform scalar offset, and the padding test is one compare per axis and tap.
+// Why the shifted base.  voffsets are unsigned, so the descriptor base is moved back by the largest negative tap
+// shift and every lane addresses its pixel's FIRST tap through it; the tap's scalar offset walks forward from
+// there.  Taps in the padding use the out-of-range voffset and are never dereferenced.
+//
+// A geometry owns what differs between the convolution forms and nothing else:
+//   Params               what the host brace-initialises (the existing structs)
+//   init(p, phase)       sets chans / plane (channel count and plane size of the gathered tensor) and the extents,
+//                        returns the shifted buffer descriptor
+//   locate(p, m, pix)    pixel index -> its first-tap coordinates and its byte offset through the shifted base;
+//                        rows past M get PAST_M in the first coordinate, so that no tap is inside for them
+//   tap(t)               tap index -> per-axis steps (run-time KW, or the phase's own nx_p / ny_p)
+//   tap_bytes(tap)       the tap's scalar byte offset
+//   inside(pix, tap)     does the tap of this pixel lie in the tensor
+// TAPGATHER marks the geometries whose igemm2 launches also build the two-wave-group kernel (igemm2_kg2_built).
+// The staging bodies are TapGatherLoader below (four waves per tile, igemm_kernel) and TapGatherA2 (gz_igemm2.h).
+// ---------------------------------------------------------------------------
+constexpr int PAST_M = -(1 << 20);
+struct Pix2 { int y, x; };
+struct Pix3 { int d, y, x; };
+
+// index -> (i / hw, row, column) of an hw = h x w grid
+__device__ __forceinline__ void unflatten(uint32_t i, FastDiv div_hw, int hw, FastDiv div_w, int w, uint32_t& n,
+                                          uint32_t& r, uint32_t& c) {
+    n = fdiv(i, div_hw);
+    const uint32_t pix = i - n * (uint32_t)hw;
+    r = fdiv(pix, div_w);
+    c = pix - r * (uint32_t)w;
+}
+
+// forward 2-D: A[m = (n, oy, ox)][k = (tap, c)] = x[n][c][oy*S-P+ky][ox*S-P+kx]
+template <int BM_, int KH, int KW, int S, int P>
+struct TapGeoFwd {
+    static constexpr int BM = BM_;
+    static constexpr bool TAPGATHER = true;
+    using Params = typename ConvFwdALoader<BM, KH, KW, S, P>::Params;
+    using Pix = Pix2;
+    int chans, plane, H, W;
+    __device__ __forceinline__ __amdgpu_buffer_rsrc_t init(const Params& p, int) {
+        const ConvShape& s = p.s;
+        chans = s.C; H = s.H; W = s.W; plane = s.H * s.W;
+        const uint32_t shift = (uint32_t)(P * s.W + P) * 4u;
+        return make_rsrc(reinterpret_cast<const char*>(p.x) - shift, (uint32_t)s.N * s.C * s.H * s.W * 4u + shift);
+    }
+    __device__ __forceinline__ uint32_t locate(const Params& p, uint32_t m, Pix& q) const {
+        const ConvShape& s = p.s;
+        uint32_t n, oy, ox;
+        unflatten(m, p.div_ohw, s.OH * s.OW, p.div_ow, s.OW, n, oy, ox);
+        q.y = m < (uint32_t)s.N * s.OH * s.OW ? (int)oy * S - P : PAST_M;
+        q.x = (int)ox * S - P;
+        return (n * (uint32_t)(chans * plane) + (uint32_t)((int)oy * S * W + (int)ox * S)) * 4u;
+    }
+    __device__ __forceinline__ Pix2 tap(int t) const { const int dy = t / KW; return {dy, t - dy * KW}; }
+    __device__ __forceinline__ uint32_t tap_bytes(const Pix2& t) const { return (uint32_t)(t.y * W + t.x) * 4u; }
+    __device__ __forceinline__ bool inside(const Pix& q, const Pix2& t) const {
+        return (unsigned)(q.y + t.y) < (unsigned)H && (unsigned)(q.x + t.x) < (unsigned)W;
+    }
+};
+
+// forward 2-D with the geometry as run-time values (rectangular kernels, per-axis stride and padding): the
+// evaluation path's InceptionV3 has 3x3 s2 p0, 5x5 s1 p2, 1x7 / 7x1, 1x3 / 3x1 ... layers (reference
+// core/submodules/gan_stability/metrics/inception.py), none of which is worth a template instantiation of its own
+// (forward only, no training step runs through them).
+template <int BM_>
+struct TapGeoFwdAny {
+    static constexpr int BM = BM_;
+    static constexpr bool TAPGATHER = true;
+    struct Params {
+        const float* x;
+        ConvShape s;
+        FastDiv div_ohw, div_ow;
+        int KH, KW, SH, SW, PH, PW;
+    };
+    using Pix = Pix2;
+    int chans, plane, H, W, KW;
+    __device__ __forceinline__ __amdgpu_buffer_rsrc_t init(const Params& p, int) {
+        const ConvShape& s = p.s;
+        chans = s.C; H = s.H; W = s.W; plane = s.H * s.W; KW = p.KW;
+        const uint32_t shift = (uint32_t)(p.PH * s.W + p.PW) * 4u;
+        return make_rsrc(reinterpret_cast<const char*>(p.x) - shift, (uint32_t)s.N * s.C * s.H * s.W * 4u + shift);
+    }
+    __device__ __forceinline__ uint32_t locate(const Params& p, uint32_t m, Pix& q) const {
+        const ConvShape& s = p.s;
+        uint32_t n, oy, ox;
+        unflatten(m, p.div_ohw, s.OH * s.OW, p.div_ow, s.OW, n, oy, ox);
+        q.y = m < (uint32_t)s.N * s.OH * s.OW ? (int)oy * p.SH - p.PH : PAST_M;
+        q.x = (int)ox * p.SW - p.PW;
+        return (n * (uint32_t)(chans * plane) + (uint32_t)((int)oy * p.SH * W + (int)ox * p.SW)) * 4u;
+    }
+    __device__ __forceinline__ Pix2 tap(int t) const { const int dy = t / KW; return {dy, t - dy * KW}; }
+    __device__ __forceinline__ uint32_t tap_bytes(const Pix2& t) const { return (uint32_t)(t.y * W + t.x) * 4u; }
+    __device__ __forceinline__ bool inside(const Pix& q, const Pix2& t) const {
+        return (unsigned)(q.y + t.y) < (unsigned)H && (unsigned)(q.x + t.x) < (unsigned)W;
+    }
+};
+
+// transposed 2-D, phase (py, px): A[m = (n, a, b)][k = (tap, ko)] = y[n][ko][oy0 - ty][ox0 - tx], tap = ty * nx + tx
+// over the phase's own ny x nx taps (dg_taps); the weight rows of a phase are packed in the same order
+// (pack_dgrad_tap), so phases with fewer taps simply have fewer chunks (the launcher passes the counts).
+// A pixel's first tap is (oy0 - (TY-1), ox0 - (TX-1)); the scalar offset walks forward to (oy0 - ty, ox0 - tx).
+template <int BM_, int KH, int KW, int S, int P>
+struct TapGeoDg {
+    static constexpr int BM = BM_;
+    static constexpr bool TAPGATHER = true;
+    static constexpr int TY = (KH + S - 1) / S, TX = (KW + S - 1) / S;
+    struct Params {
+        const float* y;
+        ConvShape s;
+        int AH, AW;
+        FastDiv div_ahw, div_aw;
+    };
+    using Pix = Pix2;
+    int chans, plane, OH, OW, nx_p, y0, x0;
+    __device__ __forceinline__ __amdgpu_buffer_rsrc_t init(const Params& p, int phase) {
+        const ConvShape& s = p.s;
+        chans = s.K; OH = s.OH; OW = s.OW; plane = s.OH * s.OW;
+        const int py = phase / S, px = phase % S;
+        nx_p = dg_taps(KW, S, P, px);
+        y0 = (py + P) / S; x0 = (px + P) / S;
+        const uint32_t shift = (uint32_t)((TY - 1) * s.OW + (TX - 1)) * 4u;
+        return make_rsrc(reinterpret_cast<const char*>(p.y) - shift, (uint32_t)s.N * s.K * s.OH * s.OW * 4u + shift);
+    }
+    __device__ __forceinline__ uint32_t locate(const Params& p, uint32_t m, Pix& q) const {
+        uint32_t n, a, b;
+        unflatten(m, p.div_ahw, p.AH * p.AW, p.div_aw, p.AW, n, a, b);
+        const int oy = (int)a + y0;
+        q.y = m < (uint32_t)p.s.N * p.AH * p.AW ? oy : PAST_M;
+        q.x = (int)b + x0;
+        return (n * (uint32_t)(chans * plane) + (uint32_t)(oy * OW + q.x)) * 4u;
+    }
+    __device__ __forceinline__ Pix2 tap(int t) const { const int ty = t / nx_p; return {ty, t - ty * nx_p}; }
+    __device__ __forceinline__ uint32_t tap_bytes(const Pix2& t) const {
+        return (uint32_t)((TY - 1 - t.y) * OW + (TX - 1 - t.x)) * 4u;
+    }
+    __device__ __forceinline__ bool inside(const Pix& q, const Pix2& t) const {
+        return (unsigned)(q.y - t.y) < (unsigned)OH && (unsigned)(q.x - t.x) < (unsigned)OW;
+    }
+};
+
+// forward 3-D (HoloGAN's ConvTranspose3d k3 s2 p1 op1, core/models/hologan_generator.py:29-30, has this as its input
+// gradient): A[m = (n, od, oy, ox)][k = (tap, c)]; weight rows follow pack_fwd3_tap (gz_conv3d.hip)
+template <int BM_, int KS, int S, int P>
+struct TapGeoFwd3D {
+    static constexpr int BM = BM_;
+    using Params = typename Conv3DFwdALoader<BM, KS, S, P>::Params;
+    using Pix = Pix3;
+    int chans, plane, D, H, W;
+    __device__ __forceinline__ __amdgpu_buffer_rsrc_t init(const Params& p, int) {
+        const Conv3DShape& s = p.s;
+        chans = s.C; D = s.D; H = s.H; W = s.W; plane = s.D * s.H * s.W;
+        const uint32_t shift = (uint32_t)((P * s.H + P) * s.W + P) * 4u;
+        return make_rsrc(reinterpret_cast<const char*>(p.x) - shift,
+                         (uint32_t)s.N * s.C * s.D * s.H * s.W * 4u + shift);
+    }
+    __device__ __forceinline__ uint32_t locate(const Params& p, uint32_t m, Pix& q) const {
+        const Conv3DShape& s = p.s;
+        const uint32_t n = fdiv(m, p.div_odhw);
+        uint32_t od, oy, ox;
+        unflatten(m - n * (uint32_t)(s.OD * s.OH * s.OW), p.div_ohw, s.OH * s.OW, p.div_ow, s.OW, od, oy, ox);
+        q.d = m < (uint32_t)s.N * s.OD * s.OH * s.OW ? (int)od * S - P : PAST_M;
+        q.y = (int)oy * S - P;
+        q.x = (int)ox * S - P;
+        return (n * (uint32_t)(chans * plane) + (uint32_t)(((int)od * S * H + (int)oy * S) * W + (int)ox * S)) * 4u;
+    }
+    __device__ __forceinline__ Pix3 tap(int t) const {
+        const int kd = t / (KS * KS), r = t - kd * (KS * KS), ky = r / KS;
+        return {kd, ky, r - ky * KS};
+    }
+    __device__ __forceinline__ uint32_t tap_bytes(const Pix3& t) const { return (uint32_t)((t.d * H + t.y) * W + t.x) * 4u; }
+    __device__ __forceinline__ bool inside(const Pix& q, const Pix3& t) const {
+        return (unsigned)(q.d + t.d) < (unsigned)D && (unsigned)(q.y + t.y) < (unsigned)H &&
+               (unsigned)(q.x + t.x) < (unsigned)W;
+    }
+};
+
+// transposed 3-D, phase (pd, py, px) (the forward of that ConvTranspose3d: 8 phases of 1..8 taps):
+// A[m = (n, a, b, c)][k = (tap, ko)] = y[n][ko][od0 - td][oy0 - ty][ox0 - tx], tap = (td * ny + ty) * nx + tx over the
+// phase's own taps and chunk count; weight rows follow pack_dgrad3_tap (gz_conv3d.hip)
+template <int BM_, int KS, int S, int P>
+struct TapGeoDg3D {
+    static constexpr int BM = BM_;
+    static constexpr int T = (KS + S - 1) / S;
+    using Params = typename Conv3DDgALoader<BM, KS, S, P>::Params;
+    using Pix = Pix3;
+    int chans, plane, OD, OH, OW, ny_p, nx_p, d0, y0, x0;
+    __device__ __forceinline__ __amdgpu_buffer_rsrc_t init(const Params& p, int phase) {
+        const Conv3DShape& s = p.s;
+        chans = s.K; OD = s.OD; OH = s.OH; OW = s.OW; plane = s.OD * s.OH * s.OW;
+        const int pd = phase / (S * S), py = (phase / S) % S, px = phase % S;
+        ny_p = dg_taps(KS, S, P, py);
+        nx_p = dg_taps(KS, S, P, px);
+        d0 = (pd + P) / S; y0 = (py + P) / S; x0 = (px + P) / S;
+        const uint32_t shift = (uint32_t)(((T - 1) * s.OH + (T - 1)) * s.OW + (T - 1)) * 4u;
+        return make_rsrc(reinterpret_cast<const char*>(p.y) - shift,
+                         (uint32_t)s.N * s.K * s.OD * s.OH * s.OW * 4u + shift);
+    }
+    __device__ __forceinline__ uint32_t locate(const Params& p, uint32_t m, Pix& q) const {
+        const uint32_t n = fdiv(m, p.div_adhw);
+        uint32_t a, b, c;
+        unflatten(m - n * (uint32_t)(p.AD * p.AH * p.AW), p.div_ahw, p.AH * p.AW, p.div_aw, p.AW, a, b, c);
+        const int od = (int)a + d0;
+        q.d = m < (uint32_t)p.s.N * p.AD * p.AH * p.AW ? od : PAST_M;
+        q.y = (int)b + y0;
+        q.x = (int)c + x0;
+        return (n * (uint32_t)(chans * plane) + (uint32_t)((od * OH + q.y) * OW + q.x)) * 4u;
+    }
+    __device__ __forceinline__ Pix3 tap(int t) const {
+        const int td = t / (ny_p * nx_p), r = t - td * (ny_p * nx_p), ty = r / nx_p;
+        return {td, ty, r - ty * nx_p};
+    }
+    __device__ __forceinline__ uint32_t tap_bytes(const Pix3& t) const {
+        return (uint32_t)(((T - 1 - t.d) * OH + (T - 1 - t.y)) * OW + (T - 1 - t.x)) * 4u;
+    }
+    __device__ __forceinline__ bool inside(const Pix& q, const Pix3& t) const {
+        return (unsigned)(q.d - t.d) < (unsigned)OD && (unsigned)(q.y - t.y) < (unsigned)OH &&
+               (unsigned)(q.x - t.x) < (unsigned)OW;
+    }
+};
+
+// The four-wave staging body (igemm_kernel): thread (m_l, kb) owns pixel m_l and the EPT channel rows kb + STEP * j
+// of every chunk; its voffsets are loop-invariant, a chunk costs one tap decode and one inside() test.
+template <class Geo_>
+struct TapGatherLoader {
+    using Geo = Geo_;
+    using Params = typename Geo::Params;
+    static constexpr int BM = Geo::BM, LD = BM;
+    static constexpr int EPT = BM * BK / NT;
+    static constexpr int STEP = NT / BM;
+    static constexpr bool DMA = GZ_IGEMM_DMA;
+    static constexpr int NPARTS = 0;
+    __device__ __forceinline__ void issue_lds_part(int, float*, int) {}
+    Geo geo;
+    __amdgpu_buffer_rsrc_t rsrc;
+    uint32_t voff[EPT];
+    typename Geo::Pix pix;
+    int kb, m_l, blocks;
+    float r[DMA ? 1 : EPT];
+    __device__ __forceinline__ void init(const Params& p, int tile, int y, int tid) {
+        rsrc = geo.init(p, y);
+        m_l = tid % BM;
+        kb = tid / BM;
+        blocks = round_bk(geo.chans) / BK;
+        const uint32_t pos = geo.locate(p, (uint32_t)tile * BM + m_l, pix);
+#pragma unroll
+        for (int j = 0; j < EPT; ++j) voff[j] = pos + (uint32_t)((kb + STEP * j) * geo.plane) * 4u;
+    }
+    // chunk -> (tap, channel block): wave-uniform
+    __device__ __forceinline__ void chunk(int kc, uint32_t& soff, bool& ok, int& cb) const {
+        const int t = kc / blocks;
+        cb = (kc - t * blocks) * BK;
+        const auto tp = geo.tap(t);
+        soff = (uint32_t)(cb * geo.plane) * 4u + geo.tap_bytes(tp);
+        ok = geo.inside(pix, tp);
+    }
+    // a wave's 64 lanes are 64 consecutive m of one k row: one contiguous 256-byte LDS piece
+    __device__ __forceinline__ void issue_lds(int kc, float* dst) {
+        float* wbase = dst + (m_l - (int)(threadIdx.x & 63));
+        uint32_t soff; bool ok; int cb;
+        chunk(kc, soff, ok, cb);
+#pragma unroll
+        for (int j = 0; j < EPT; ++j)
+            bload_lds4(rsrc, wbase + (kb + STEP * j) * LD, (ok && cb + kb + STEP * j < geo.chans) ? voff[j] : OOB, soff);
+    }
+    __device__ __forceinline__ void issue(int kc) {
+        if constexpr (!DMA) {
+            uint32_t soff; bool ok; int cb;
+            chunk(kc, soff, ok, cb);
+#pragma unroll
+            for (int j = 0; j < EPT; ++j)
+                r[j] = bload(rsrc, (ok && cb + kb + STEP * j < geo.chans) ? voff[j] : OOB, soff);
+        }
+    }
+    __device__ __forceinline__ void commit(float* dst) const {
+        if constexpr (!DMA) {
+#pragma unroll
+            for (int j = 0; j < EPT; ++j) dst[(kb + STEP * j) * LD + m_l] = r[j];
+        }
+    }
+};
+
+template <int BM, int KH, int KW, int S, int P>
+using ConvFwdALoaderTap = TapGatherLoader<TapGeoFwd<BM, KH, KW, S, P>>;
+template <int BM>
+using ConvFwdALoaderTapAny = TapGatherLoader<TapGeoFwdAny<BM>>;
+template <int BM, int KH, int KW, int S, int P>
+using ConvDgALoaderTap = TapGatherLoader<TapGeoDg<BM, KH, KW, S, P>>;
+template <int BM, int KS, int S, int P>
+using Conv3DFwdALoaderTap = TapGatherLoader<TapGeoFwd3D<BM, KS, S, P>>;
 
 }  // namespace gz

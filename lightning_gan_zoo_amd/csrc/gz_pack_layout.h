@@ -16,8 +16,8 @@ __host__ __device__ constexpr int dg_taps(int KS, int S, int P, int parity) {
 constexpr int round_bk(int v) { return (v + BK - 1) / BK * BK; }
 __host__ __device__ constexpr int round4(int v) { return (v + 3) & ~3; }
 
-// Tap-major reduction order (gz_igemm.h: ConvFwdALoaderTap / ConvDgALoaderTap) is used when the tap count does not
-// divide a chunk (3x3, 5x5) and there are enough channels to fill the BK-wide channel blocks.
+// Tap-major reduction order (gz_igemm_loaders.h: the TapGeo* geometries under TapGatherLoader / TapGatherA2) is used
+// when the tap count does not divide a chunk (3x3, 5x5) and there are enough channels to fill the BK-wide channel blocks.
 inline bool fwd_tap_major(int C, int KH, int KW) {
     return !knobs().no_tapmajor && (BK % (KH * KW) != 0) && C >= BK;
 }

@@ -150,7 +150,9 @@ def test_state_dict_layout_is_torchvisions():
     # round 6: launches that fill the chip with 256x64 tiles take the igemm2 skeleton (ConvTapAnyA2 + EpiNCHWBiasAct):
     # 1x7 / 7x1 with asymmetric padding, 5x5 p2 on 48 channels (three channel blocks), 3x3 stride 2, 1x1; ragged last tiles
     (72, 128, 17, 17, 192, 1, 7, 1, 1, 0, 3), (72, 160, 17, 17, 192, 7, 1, 1, 1, 3, 0), (48, 48, 35, 35, 64, 5, 5, 1, 1, 2, 2),
-    (64, 288, 35, 35, 384, 3, 3, 2, 2, 0, 0), (96, 256, 17, 17, 192, 1, 1, 1, 1, 0, 0), (40, 64, 33, 37, 128, 3, 3, 1, 1, 1, 1)])
+    (64, 288, 35, 35, 384, 3, 3, 2, 2, 0, 0), (96, 256, 17, 17, 192, 1, 1, 1, 1, 0, 0), (40, 64, 33, 37, 128, 3, 3, 1, 1, 1, 1),
+    # ... 72 channels (the last channel block of a tap half empty) under a ragged last pixel tile (11560 pixels = 45.2 tiles)
+    (40, 72, 17, 17, 320, 1, 7, 1, 1, 0, 3)])
 def test_conv2d_fwd_any(case):
     from lightning_gan_zoo_amd import functional as F
     from lightning_gan_zoo_amd._lib import check, lib

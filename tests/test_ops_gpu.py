@@ -459,7 +459,11 @@ def test_gp_tail_ops():
                                   (64, 512, 4, 128),      # HoloGAN block1 at the benched bs 64: 27 slabs over 8 phases
                                   (3, 64, 4, 64),         # igemm2 gathers with fewer rows than one 256-row tile
                                   (2, 192, 4, 192),       # ... 192 columns: three 64-wide tiles, ragged 16-channel blocks
-                                  (5, 72, 8, 64)])        # ... 72 input channels: the last channel block is half empty
+                                  (5, 72, 8, 64),         # ... 72 input channels: the last channel block is half empty
+                                  # ragged last pixel tile AND a half-empty last channel block, one case per tap-major gather
+                                  (5, 72, 4, 128),        # Dg on Conv3DDgTapA2: 320 pixels per phase, 72 feature channels
+                                  (24, 512, 5, 72),       # F on Conv3DTapA2: 3000 pixels, 72 image-side channels
+                                  (2, 24, 3, 20)])        # F on Conv3DFwdALoaderTap: 54 pixels, 20 image-side channels
 def test_conv3d_family(case):
     """ConvTranspose3d(k3,s2,p1,op1) forward (Dg), its input gradient (F) and weight gradient (Wg)."""
     F = _F()
@@ -1507,6 +1511,7 @@ IGEMM2_TAP_DG_S1_CASES = [
     (8, 256, 32, 512, 3, 1),          # 32 x 2 tiles, 288 chunks -> 4 splits
     (64, 1024, 16, 1024, 1, 0),       # HoloGAN's 1x1 transposed convolution (forward)
     (70, 160, 32, 200, 1, 0),         # 1x1, ragged everything
+    (50, 256, 24, 136, 3, 1),         # 3x3 with a ragged last pixel tile (28800 pixels = 112.5 tiles) and 136 feature channels
 ]
 
 
