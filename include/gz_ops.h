@@ -225,7 +225,16 @@ int gz_rigid_resample_fwd(const float* vox, const float* minv, float* out2d, lon
                           hipStream_t stream);
 /* gvox [N,C,S,S,S] = adjoint of the above in gather form (no atomics, every element written once): per-voxel hit
  * lists in `workspace` (gz_rigid_resample_bwd_workspace_bytes), gradient volumes staged through LDS.  workspace
- * NULL / too small: the same result from the slower direct gather. */
+ * NULL / too small: the same result from the slower direct gather.
+ * A list holds at most gz_rigid_resample_bwd_list_capacity() hits; one source voxel with more (views that zoom in)
+ * makes the whole launch take the direct gather.  Which of the two ran is decided on the device; after a call that was
+ * given a sufficient workspace (16-byte aligned, as gout2d; S^3 % 4 == 0, S <= 16) it can be read back from the
+ * workspace, in stream order, with capacity = gz_rigid_resample_bwd_list_capacity():
+ *   - the int32 at byte offset gz_rigid_resample_bwd_workspace_bytes(N, S) - 16 is non-zero exactly when a list
+ *     overflowed and the direct gather produced gvox;
+ *   - the int32 plane [N*S^3] at byte offset capacity * N*S^3 * 4 holds min(hits, capacity) per source voxel
+ *     (index n*S^3 + (z*S + y)*S + x). */
+int gz_rigid_resample_bwd_list_capacity(void);
 size_t gz_rigid_resample_bwd_workspace_bytes(int N, int S);
 int gz_rigid_resample_bwd(const float* gout2d, const float* minv, float* gvox, float* workspace, size_t ws_bytes,
                           int N, int C, int S, hipStream_t stream);

@@ -506,6 +506,8 @@ int gz_rigid_resample_views_fwd(const float* vox, const float* minv, float* out2
     return launch_status();
 }
 
+int gz_rigid_resample_bwd_list_capacity(void) { return BH; }
+
 size_t gz_rigid_resample_bwd_workspace_bytes(int N, int S) {
     if (N <= 0 || S <= 0) return 0;
     return (size_t)N * S * S * S * (BH * 8 + 4) + 16;      // hit offsets + lengths, weights, the overflow flag

@@ -28,6 +28,19 @@ def test_size_queries_need_no_gpu():
     assert lib.gz_norm_coef_elems(4, 8, 1) == 32 and lib.gz_norm_coef_elems(4, 8, 0) == 128
 
 
+def test_resample_workspace_words_lie_where_the_header_says():
+    """gz_ops.h: list-length plane at byte capacity * N*S^3 * 4, overflow flag 16 bytes before the end; between them the
+    weight planes, so both stay inside the advertised size."""
+    lib = _lib.lib
+    cap = lib.gz_rigid_resample_bwd_list_capacity()
+    assert cap > 0
+    for N, S in ((1, 4), (6, 16), (3, 20)):
+        ns3 = N * S ** 3
+        nbytes = lib.gz_rigid_resample_bwd_workspace_bytes(N, S)
+        assert nbytes == ns3 * (cap * 8 + 4) + 16
+        assert (cap + 1) * ns3 * 4 <= nbytes - 16 and (nbytes - 16) % 16 == 0
+
+
 def test_product_path_fails_loudly_on_cpu_tensors():
     from lightning_gan_zoo_amd.core.models.standard_networks import Discriminator, Generator
     g, d = Generator(16, 3, 8), Discriminator(3, 8, final_sigmoid=False)

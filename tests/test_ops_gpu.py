@@ -558,7 +558,9 @@ def test_row_norms_keep_their_digits_when_the_mean_dwarfs_the_spread(inner_shape
 
 def test_rigid_resample_matches_oracle_and_indices_are_bit_exact():
     """int64 voxel indices (reference idx_a..idx_h) bit-exact; resampled features and their adjoint
-    within 1e-3 (observed 1e-6)."""
+    within 1e-3 (observed 1e-6).  Its forward values come from the direct kernel (idx_out is passed) and its backward
+    from the gather fallback (the scale-2 view overflows the hit lists); the forms that run are checked in
+    test_resample_gpu.py."""
     F = _F()
     import numpy as np
     from oracle import hologan_cpu as H
