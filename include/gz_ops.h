@@ -550,6 +550,23 @@ int gz_ema_job(void* job_out, float* avg, const float* src, long long numel, int
 int gz_ema_update(const void* jobs_dev, int count, int total_blocks, float beta, float one_minus_beta,
                   hipStream_t stream);
 
+/* ---- KID on the device (reference core/callback_inception_metrics.py:15-133) ----------------------------------------
+ * Everything `_mmd2_and_variance` reads of the three polynomial-kernel matrices of S subsets, in fp64 on
+ * v_mfma_f64_16x16x4_f64, without a kernel matrix in memory.  codes_g [n_g, d] and codes_r [n_r, d] are fp64 row-major
+ * DEVICE arrays, idx [S][2][m] int32 DEVICE row numbers into codes_g (slot 0) and codes_r (slot 1), gathered on load.
+ * With G = codes_g[idx[s][0]], R = codes_r[idx[s][1]] and K_AB = (gamma * A B^T + coef0)^degree (repeated
+ * multiplication, degree >= 1), out [S][6*m + 3] receives per subset
+ *     rowsum(K_GG) (diagonal included) | diag(K_GG) | rowsum(K_RR) | diag(K_RR) | rowsum(K_GR) | colsum(K_GR) |
+ *     |K_GG|_F^2, |K_RR|_F^2, |K_GR|_F^2.
+ * d and m need no multiple of anything.  Deterministic: no floating-point atomics, a fixed order for every sum, and
+ * neither `out` nor the workspace (gz_kid_workspace_bytes bytes) has to be zeroed.  Two launches on `stream`.
+ * GZ_ERR_BAD_SHAPE: S, m, d, degree, n_g or n_r below 1, m > min(n_g, n_r), a null pointer; GZ_ERR_WORKSPACE: workspace
+ * too short (nothing is launched).  The index VALUES are the caller's contract: they are not checked here. */
+size_t gz_kid_workspace_bytes(int S, int m, int d);
+int gz_kid_sums(const double* codes_g, int n_g, const double* codes_r, int n_r, int d, const int* idx, int S, int m,
+                double gamma, double coef0, int degree, double* out, void* workspace, size_t ws_bytes,
+                hipStream_t stream);
+
 /* text of the last HIP error seen by a launcher on the calling thread ("" if none) */
 const char* gz_last_error(void);
 

@@ -16,7 +16,7 @@ ERRORS = {-1: "bad shape / alignment", -2: "unsupported configuration", -3: "wor
           -4: "HIP error", -5: "tensor too large for 32-bit buffer addressing"}
 
 _C = {
-    "int": ctypes.c_int, "float": ctypes.c_float, "size_t": ctypes.c_size_t,
+    "int": ctypes.c_int, "float": ctypes.c_float, "double": ctypes.c_double, "size_t": ctypes.c_size_t,
     "long long": ctypes.c_longlong, "hipStream_t": ctypes.c_void_p, "void": None,
     "const char*": ctypes.c_char_p,
 }

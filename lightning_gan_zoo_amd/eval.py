@@ -11,7 +11,8 @@ SURVEY.md 8-f3) minus the Inception network itself, whose weights are fetched fr
 
 ``evaluate`` strings them together around any ``feature_fn(images_uint8_nhwc) -> [n, d]`` feature extractor.
 The arithmetic is pinned to the reference's own functions by tests/golden/eval_metrics.npz
-(tests/golden/make_eval_golden.py).  Host-side numpy / scipy like the reference; only the generator runs on the GPU.
+(tests/golden/make_eval_golden.py).  Host-side numpy / scipy like the reference; only the generator runs on the GPU -- and, opt-in
+(``kid_on_device``), KID's kernel-matrix sums (``polynomial_mmd_averages_device``, csrc/gz_kid.hip).
 """
 import numpy as np
 import torch
@@ -170,14 +171,128 @@ def polynomial_mmd_averages(codes_g, codes_r, n_subsets=50, subset_size=1000, re
     return (mmds, variances) if ret_var else mmds
 
 
-def evaluate(module, dump, feature_fn, real_act, n_subsets=100):
+def _mmd2_and_variance_from_sums(sums, m, var_at_m=None, ret_var=True):
+    """``_mmd2_and_variance`` for S subsets at once, from the ``6 m + 3`` numbers per subset that gz_kid_sums writes
+    (include/gz_ops.h): rowsum(K_xx) with the diagonal | diag(K_xx) | rowsum(K_yy) | diag(K_yy) | rowsum(K_xy) |
+    colsum(K_xy) | the three squared Frobenius norms -- all the estimator reads of the matrices.  ``sums``: [S, 6m+3]."""
+    sums = np.asarray(sums, dtype=np.float64)
+    if sums.ndim != 2 or sums.shape[1] != 6 * m + 3:
+        raise ValueError("expected [S, %d] sums for m = %d, got %s" % (6 * m + 3, m, sums.shape))
+    if var_at_m is None:
+        var_at_m = m
+    dx, dy = sums[:, m:2 * m], sums[:, 3 * m:4 * m]
+    rx = sums[:, :m] - dx                   # row sums without the diagonal
+    ry = sums[:, 2 * m:3 * m] - dy
+    cxy1, cxy0 = sums[:, 4 * m:5 * m], sums[:, 5 * m:6 * m]
+    sx, sy, sxy = rx.sum(axis=1), ry.sum(axis=1), cxy0.sum(axis=1)
+    mmd2 = (sx + sy) / (m * (m - 1)) - 2 * sxy / (m * m)
+    if not ret_var:
+        return mmd2
+
+    def sq(a):
+        return np.einsum("sm,sm->s", a, a)
+
+    sx2 = sums[:, 6 * m] - sq(dx)
+    sy2 = sums[:, 6 * m + 1] - sq(dy)
+    sxy2 = sums[:, 6 * m + 2]
+    dxx = np.einsum("sm,sm->s", rx, cxy1)
+    dyy = np.einsum("sm,sm->s", ry, cxy0)
+    m1, m2 = m - 1, m - 2
+    zeta1 = (1 / (m * m1 * m2) * (sq(rx) - sx2 + sq(ry) - sy2)
+             - 1 / (m * m1) ** 2 * (sx ** 2 + sy ** 2)
+             + 1 / (m * m * m1) * (sq(cxy1) + sq(cxy0) - 2 * sxy2)
+             - 2 / m ** 4 * sxy ** 2
+             - 2 / (m * m * m1) * (dxx + dyy)
+             + 2 / (m ** 3 * m1) * (sx + sy) * sxy)
+    zeta2 = (1 / (m * m1) * (sx2 + sy2)
+             - 1 / (m * m1) ** 2 * (sx ** 2 + sy ** 2)
+             + 2 / (m * m) * sxy2
+             - 2 / m ** 4 * sxy ** 2
+             - 4 / (m * m * m1) * (dxx + dyy)
+             + 4 / (m ** 3 * m1) * (sx + sy) * sxy)
+    var = 4 * (var_at_m - 2) / (var_at_m * (var_at_m - 1)) * zeta1 + 2 / (var_at_m * (var_at_m - 1)) * zeta2
+    return mmd2, var
+
+
+def draw_kid_subsets(n_g, n_r, n_subsets, subset_size):
+    """The rows ``polynomial_mmd_averages`` would pick: the same ``np.random.choice(..., replace=False)`` calls on
+    numpy's GLOBAL generator in the same order (g then r, subset after subset), so the generator is left in the state
+    the host loop leaves it in.  ``subset_size`` is clamped like there.  -> int32 [n_subsets, 2, m]."""
+    m = min(n_g, n_r, subset_size)
+    idx = np.empty((n_subsets, 2, m), dtype=np.int32)
+    for i in range(n_subsets):
+        idx[i, 0] = np.random.choice(n_g, m, replace=False)
+        idx[i, 1] = np.random.choice(n_r, m, replace=False)
+    return idx
+
+
+def device_codes(codes, device):
+    """[n, d] codes as a contiguous fp64 tensor on ``device`` (fp32 is widened there: exact)."""
+    t = codes if isinstance(codes, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(codes))
+    if t.dim() != 2 or not (t.dtype.is_floating_point or t.dtype in (torch.int32, torch.int64)):
+        raise ValueError("codes must be a real [n, d] array, got %s %s" % (t.dtype, tuple(t.shape)))
+    t = t.detach().to(device).to(torch.float64).contiguous()
+    if not t.is_cuda:
+        raise RuntimeError("lightning_gan_zoo_amd.eval: the device KID path runs on the HIP kernels; device %r is not a "
+                           "GPU and there is no fallback (use polynomial_mmd_averages)" % (device,))
+    return t
+
+
+def kid_sums_device(codes_g, codes_r, idx, degree=3, gamma=None, coef0=1):
+    """gz_kid_sums (csrc/gz_kid.hip) on fp64 device codes for the host index table ``idx`` [S, 2, m] (checked here: the
+    kernel trusts it).  One upload of the indices, two launches, one copy back.  -> numpy [S, 6m+3]."""
+    from . import functional as F
+    from ._lib import check, lib
+    idx = np.ascontiguousarray(idx, dtype=np.int32)
+    if idx.ndim != 3 or idx.shape[1] != 2 or idx.size == 0:
+        raise ValueError("idx must be a non-empty [S, 2, m] table, got %s" % (idx.shape,))
+    S, _, m = idx.shape
+    (n_g, d), n_r = codes_g.shape, codes_r.shape[0]
+    if codes_r.shape[1] != d:
+        raise ValueError("the two code sets have different dimensions (%d, %d)" % (d, codes_r.shape[1]))
+    if idx.min() < 0 or idx[:, 0].max() >= n_g or idx[:, 1].max() >= n_r:
+        raise ValueError("subset rows outside the code sets")
+    if gamma is None:
+        gamma = 1.0 / d
+    with torch.cuda.device(codes_g.device):
+        idx_dev = torch.from_numpy(idx).to(codes_g.device)
+        out = torch.empty((S, 6 * m + 3), dtype=torch.float64, device=codes_g.device)
+        ws_bytes = lib.gz_kid_workspace_bytes(S, m, d)
+        ws = torch.empty(max(ws_bytes, 8), dtype=torch.uint8, device=codes_g.device)
+        check(lib.gz_kid_sums(F._p(codes_g), n_g, F._p(codes_r), n_r, d, F._p(idx_dev), S, m, float(gamma), float(coef0),
+                              int(degree), F._p(out), F._p(ws), ws_bytes, F._stream()), "kid_sums")
+        return out.cpu().numpy()
+
+
+def polynomial_mmd_averages_device(codes_g, codes_r, n_subsets=50, subset_size=1000, ret_var=True, degree=3, gamma=None,
+                                   coef0=1, device="cuda"):
+    """``polynomial_mmd_averages`` with the kernel matrices' sums computed on the GPU (csrc/gz_kid.hip, fp64 MFMA): the
+    same subsets from numpy's global generator, left in the same state; the same values up to the order of fp64
+    summation.  ``codes_*``: numpy arrays or torch tensors (tensors already on the device in fp64 are used as they
+    are); the estimator's O(S m) formula runs on the host."""
+    g, r = device_codes(codes_g, device), device_codes(codes_r, device)
+    if r.device != g.device:
+        r = r.to(g.device)
+    idx = draw_kid_subsets(g.shape[0], r.shape[0], n_subsets, subset_size)
+    sums = kid_sums_device(g, r, idx, degree=degree, gamma=gamma, coef0=coef0)
+    return _mmd2_and_variance_from_sums(sums, idx.shape[2], var_at_m=min(g.shape[0], r.shape[0]), ret_var=ret_var)
+
+
+def evaluate(module, dump, feature_fn, real_act, n_subsets=100, kid_on_device=False, real_codes_device=None):
     """FID / KID of ``module.generator`` against real activations ``real_act`` (:205-238) with a pluggable
-    feature extractor in place of InceptionV3's 2048-d pool features."""
+    feature extractor in place of InceptionV3's 2048-d pool features.  ``kid_on_device``: KID through
+    ``polynomial_mmd_averages_device`` on the module's GPU; FID stays on the host either way.  ``real_codes_device``:
+    ``device_codes(real_act, module.device)`` made once by a caller that evaluates every epoch (``real_act`` does not
+    change between epochs), so that the real codes are uploaded once per run; without it they are uploaded per call."""
     fake_act = np.concatenate([np.asarray(feature_fn(img)) for img in dump.images(module)], axis=0)
     real_mu, real_sigma = activation_statistics(real_act)
     fake_mu, fake_sigma = activation_statistics(fake_act)
     fid = frechet_distance(real_mu, real_sigma, fake_mu, fake_sigma)
-    kid = polynomial_mmd_averages(np.asarray(real_act), fake_act, n_subsets=n_subsets)
+    if kid_on_device:
+        real_codes = real_act if real_codes_device is None else real_codes_device
+        kid = polynomial_mmd_averages_device(real_codes, fake_act, n_subsets=n_subsets, device=module.device)
+    else:
+        kid = polynomial_mmd_averages(np.asarray(real_act), fake_act, n_subsets=n_subsets)
     return {"fid": fid, "kid": float(kid[0].mean()), "kid_std": float(kid[0].std())}
 
 

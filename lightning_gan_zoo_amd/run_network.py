@@ -42,7 +42,10 @@ RUNNER_KEYS = {"max_steps": None, "log_every": 10, "dataset_path": None, "seed":
                "resident_data": False, "data_cache": None, "resident_max_gb": 32,
                # exponential moving average of the generator's weights (averaging.py; gan_stability's update_average with
                # its model_average_beta default): evaluation, figures and checkpoints see the averaged generator
-               "generator_average": False, "generator_average_beta": 0.999}
+               "generator_average": False, "generator_average_beta": 0.999,
+               # KID's kernel-matrix sums on the GPU (eval.polynomial_mmd_averages_device, csrc/gz_kid.hip) instead of
+               # ~a minute of host fp64 GEMMs per evaluation; FID stays on the host
+               "kid_on_device": False}
 BUILTIN_DATASETS = ("synthetic", "image_folder", "tensor_file", "celeb_a", "mnist")
 AVERAGE_PREFIX = "generator_average."     # state_dict keys of the averaged generator's parameters, next to generator.*
 LIGHTNING_VERSION_TAG = "1.2.0"       # envelope layout written below (Lightning 1.1 / 1.2 generation)
@@ -703,10 +706,14 @@ def make_fid_evaluator(cfg, run, module, device, average=None):
     # parallelism the other ranks wait for it ONCE, at start-up (main() gives the process group a long timeout), not
     # inside a collective in the middle of the run
     real_act = real_activations(val_root, features)
+    kid_on_device = bool(run.get("kid_on_device", False))
+    # real_act is the same every epoch: its fp64 device copy is made once per run, here
+    real_codes = E.device_codes(real_act, device) if kid_on_device else None
 
     def evaluate(mod, epoch):
         with rendering_from(mod, average):          # generator_average=true: the averaged generator is what is scored
-            m = E.evaluate(mod, dump, features, real_act)
+            m = E.evaluate(mod, dump, features, real_act, kid_on_device=kid_on_device,
+                           real_codes_device=real_codes)
         print("epoch %d FID: %.4f KID mean: %.6f KID stddev: %.6f" % (epoch, m["fid"], m["kid"], m["kid_std"]))
         return m
 
