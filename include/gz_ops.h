@@ -278,6 +278,14 @@ int gz_pool2d(const float* x, float* y, long long planes, int H, int W, int OH, 
 /* y = F.interpolate(x, (OH, OW), mode='bilinear', align_corners=False) * mul + add */
 int gz_resize_bilinear(const float* x, float* y, long long planes, int H, int W, int OH, int OW, float mul, float add,
                        hipStream_t stream);
+/* Generator output -> InceptionV3 input in one launch (the device evaluation pass, eval.SampleDump.device_batches):
+ * x [N, C, H, W] with C = 1 or 3, y [N, 3, OH, OW] = bilinear(q(x)) * mul + add, q(v) = ToTensor of the grey level
+ * trunc(clamp(v, 0, 1) * 255) -- the callback's clamp -> (samples * 255).astype(int) -> PNG -> ToTensor, in fp32.  For
+ * C = 1 the single plane feeds all three output channels.  Bit-equal to quantising on the host, then gz_u8hwc_to_nchw
+ * (mean 0, std 1), then gz_resize_bilinear(..., mul, add): the three share their expressions.  GZ_ERR_BAD_SHAPE: a size
+ * below 1, another C, a null pointer. */
+int gz_samples_to_inception_input(const float* x, float* y, int N, int C, int H, int W, int OH, int OW, float mul,
+                                  float add, hipStream_t stream);
 
 /* ---- loss heads and the scalar side of spectral normalisation (csrc/gz_loss.hip) -----------------------------
  * Scalars (loss, sigma, the incoming loss gradient) are 1-element DEVICE arrays: nothing synchronises with the host.
@@ -566,6 +574,18 @@ size_t gz_kid_workspace_bytes(int S, int m, int d);
 int gz_kid_sums(const double* codes_g, int n_g, const double* codes_r, int n_r, int d, const int* idx, int S, int m,
                 double gamma, double coef0, int degree, double* out, void* workspace, size_t ws_bytes,
                 hipStream_t stream);
+
+/* ---- activation statistics on the device (reference core/callback_inception_metrics.py:223-231) -----------------------
+ * mean [d] and cov [d][d] = np.cov(act, rowvar=False) of act [n][d], fp64 row-major DEVICE arrays, on
+ * v_mfma_f64_16x16x4_f64 (csrc/gz_moments.hip).  numpy's two-pass form in numpy's order: column means, c = x - mean as
+ * the values are loaded, cov = (C^T C) * (1.0 / (n - 1)).  n and d need no multiple of anything; row offsets are 64-bit.
+ * Deterministic: no floating-point atomics, a fixed order for every sum, and neither the outputs nor the workspace
+ * (gz_feature_moments_workspace_bytes bytes) has to be zeroed; two calls give equal bits, and cov[i][j] and cov[j][i]
+ * are the same bits (upper-triangle tiles, mirrored by the epilogue).  Three launches on `stream`.
+ * GZ_ERR_BAD_SHAPE: n < 2, d < 1, a null pointer; GZ_ERR_WORKSPACE: workspace too short (nothing is launched). */
+size_t gz_feature_moments_workspace_bytes(long long n, int d);
+int gz_feature_moments(const double* act, long long n, int d, double* mean, double* cov, void* workspace,
+                       size_t ws_bytes, hipStream_t stream);
 
 /* text of the last HIP error seen by a launcher on the calling thread ("" if none) */
 const char* gz_last_error(void);

@@ -60,6 +60,11 @@ __device__ __forceinline__ uint32_t fdiv(uint32_t n, const FastDiv& f) {
     return (t + ((n - t) >> f.sh1)) >> f.sh2;
 }
 
+// the one expression of the input step: (x / 255 - mean) / std as x * scale + shift.  Every kernel that turns a grey
+// level into a float calls it (gz_resnet.hip's two input kernels, gz_infer.hip's fused Inception input), so the compiler
+// contracts (or does not contract) the multiply-add the same way in all of them and their results agree bit for bit.
+__device__ __forceinline__ float u8_norm(unsigned char v, float scale, float shift) { return (float)v * scale + shift; }
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);

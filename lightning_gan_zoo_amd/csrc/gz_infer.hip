@@ -1,6 +1,6 @@
 // Evaluation-path helpers (the InceptionV3 feature extractor behind FID / KID, reference
 // core/callback_inception_metrics.py:183-246, core/submodules/gan_stability/metrics/inception.py): 2-D pooling,
-// bilinear resize.  One lane per output element, lanes along the row; forward only.
+// bilinear resize, generator output -> Inception input.  One lane per output element, lanes along the row; forward only.
 #include "gz_common.h"
 #include "gz_knobs.h"
 #include "../../include/gz_ops.h"
@@ -204,7 +204,44 @@ static void launch_pool_group(const float* x, float* y, int planes, int H, int W
 }
 
 // F.interpolate(mode='bilinear', align_corners=False) followed by  out * mul + add  (inception.py:141-149: resize to
-// 299 x 299, then 2x - 1)
+// 299 x 299, then 2x - 1) at output pixel (oy, ox) of one plane; `px(i)` is the plane's value at flat index i.  The one
+// interpolation both kernels below call.
+//
+// Which products of  hy * (hx a + lx b) + ly * (hx c + lx d)  the compiler fuses is not a property of the expression:
+// in resize_bilinear_kernel's grid-stride loop the vectorised pairs of iterations get  fma(hy, top, ly * bot)  with
+// top = fma(lx, b, hx a), bot = fma(lx, d, hx c), and the remainder iteration -- every pixel of a launch of up to 2^20
+// outputs, where no thread loops -- gets  hy * top + ly * bot  unfused with  bot = fma(hx, c, lx d).  That kernel keeps the
+// plain expression (PINNED = false) and with it, instruction for instruction, the code and the bits it had
+// (tests/golden/eval_input_parent.npz).  The fused input kernel takes PINNED = true: the remainder iteration's
+// operations spelled out with contraction off, so that it agrees bit for bit with the resize of a materialised plane
+// wherever that resize does not depend on the pixel's place in the launch.
+template <bool PINNED, class Px>
+__device__ __forceinline__ float bilinear_sample(Px px, int oy, int ox, int H, int W, float sh, float sw, float mul,
+                                                 float add) {
+    // ATen's area_pixel_compute_source_index (align_corners=False): max(0, (dst + 0.5) * scale - 0.5)
+    float fy, fx;
+    if constexpr (PINNED) {
+        fy = fmaxf(__builtin_fmaf(oy + 0.5f, sh, -0.5f), 0.f), fx = fmaxf(__builtin_fmaf(ox + 0.5f, sw, -0.5f), 0.f);
+    } else {
+        fy = fmaxf((oy + 0.5f) * sh - 0.5f, 0.f), fx = fmaxf((ox + 0.5f) * sw - 0.5f, 0.f);
+    }
+    const int y0 = (int)fy, x0 = (int)fx;
+    const int y1 = y0 + (y0 < H - 1 ? 1 : 0), x1 = x0 + (x0 < W - 1 ? 1 : 0);
+    const float ly = fy - (float)y0, lx = fx - (float)x0;
+    const float hy = 1.f - ly, hx = 1.f - lx;
+    if constexpr (PINNED) {
+#pragma clang fp contract(off)
+        const float top = __builtin_fmaf(lx, px(y0 * W + x1), hx * px(y0 * W + x0));
+        const float bot = __builtin_fmaf(hx, px(y1 * W + x0), lx * px(y1 * W + x1));
+        const float v = hy * top + ly * bot;
+        return __builtin_fmaf(v, mul, add);
+    } else {
+        const float v = hy * (hx * px(y0 * W + x0) + lx * px(y0 * W + x1)) +
+                        ly * (hx * px(y1 * W + x0) + lx * px(y1 * W + x1));
+        return v * mul + add;
+    }
+}
+
 __global__ __launch_bounds__(IT) void resize_bilinear_kernel(const float* __restrict__ x, float* __restrict__ y,
                                                             long long total, int H, int W, int OH, int OW, float sh,
                                                             float sw, float mul, float add) {
@@ -215,15 +252,34 @@ __global__ __launch_bounds__(IT) void resize_bilinear_kernel(const float* __rest
         const int oy = (int)(t % OH);
         const long long plane = t / OH;
         const float* src = x + plane * H * W;
-        // ATen's area_pixel_compute_source_index (align_corners=False): max(0, (dst + 0.5) * scale - 0.5)
-        const float fy = fmaxf((oy + 0.5f) * sh - 0.5f, 0.f), fx = fmaxf((ox + 0.5f) * sw - 0.5f, 0.f);
-        const int y0 = (int)fy, x0 = (int)fx;
-        const int y1 = y0 + (y0 < H - 1 ? 1 : 0), x1 = x0 + (x0 < W - 1 ? 1 : 0);
-        const float ly = fy - (float)y0, lx = fx - (float)x0;
-        const float hy = 1.f - ly, hx = 1.f - lx;
-        const float v = hy * (hx * src[y0 * W + x0] + lx * src[y0 * W + x1]) +
-                        ly * (hx * src[y1 * W + x0] + lx * src[y1 * W + x1]);
-        y[i] = v * mul + add;
+        y[i] = bilinear_sample<false>([src](int j) { return src[j]; }, oy, ox, H, W, sh, sw, mul, add);
+    }
+}
+
+// Generator output -> Inception input in one launch: the sample dump's clamp to [0, 1] and truncation to a grey level
+// (reference core/callback_inception_metrics.py:197-198, `(samples * 255).astype(int)`), ToTensor's level / 255
+// (u8_norm with mean 0, std 1), the resize and 2x - 1.  A source pixel is quantised where it is read, four per output
+// pixel: the input is 0.05 of the output at 64 -> 299 and stays in cache, so no quantised plane exists in memory.
+// Output plane n*3 + c reads input plane n*C + (C == 1 ? 0 : c); blockIdx.y walks the planes, 32-bit indices inside one.
+__device__ __forceinline__ float quantised_level(float v, float scale, float shift) {
+    const float c = fminf(fmaxf(v, 0.f), 1.f);
+    return u8_norm((unsigned char)(int)(c * 255.0f), scale, shift);
+}
+
+__global__ __launch_bounds__(IT) void samples_to_inception_kernel(const float* __restrict__ x, float* __restrict__ y,
+                                                                 int planes, int C, int H, int W, int OH, int OW,
+                                                                 float sh, float sw, float mul, float add, float scale,
+                                                                 float shift, gz::FastDiv div_ow) {
+    const int ohw = OH * OW;
+    for (int pl = blockIdx.y; pl < planes; pl += gridDim.y) {
+        const int n = pl / 3, c = pl - n * 3;
+        const float* src = x + ((long long)n * C + (C == 1 ? 0 : c)) * H * W;
+        float* dst = y + (long long)pl * ohw;
+        for (int i = blockIdx.x * IT + threadIdx.x; i < ohw; i += gridDim.x * IT) {
+            const int oy = (int)gz::fdiv((uint32_t)i, div_ow), ox = i - oy * OW;
+            dst[i] = bilinear_sample<true>([src, scale, shift](int j) { return quantised_level(src[j], scale, shift); }, oy, ox,
+                                     H, W, sh, sw, mul, add);
+        }
     }
 }
 
@@ -289,6 +345,23 @@ int gz_resize_bilinear(const float* x, float* y, long long planes, int H, int W,
     const long long total = planes * OH * OW;
     hipLaunchKernelGGL(resize_bilinear_kernel, dim3(infer_grid(total)), dim3(IT), 0, stream, x, y, total, H, W, OH, OW,
                        (float)H / (float)OH, (float)W / (float)OW, mul, add);
+    return launch_status();
+}
+
+int gz_samples_to_inception_input(const float* x, float* y, int N, int C, int H, int W, int OH, int OW, float mul,
+                                  float add, hipStream_t stream) {
+    gz::clear_stale_error();
+    if (N <= 0 || (C != 1 && C != 3) || H <= 0 || W <= 0 || OH <= 0 || OW <= 0 || !x || !y) return GZ_ERR_BAD_SHAPE;
+    if ((long long)H * W >= (1ll << 31) || (long long)OH * OW >= (1ll << 31) || (long long)N * 3 >= (1ll << 31))
+        return GZ_ERR_TOO_LARGE;
+    const int planes = N * 3, ohw = OH * OW;
+    int gx = (ohw + IT - 1) / IT;
+    gx = gx > 4096 ? 4096 : gx;
+    const int gy = planes < 65535 ? planes : 65535;
+    const float mean = 0.f, std = 1.f;                   // ToTensor alone; the expressions of gz_u8hwc_to_nchw
+    hipLaunchKernelGGL(samples_to_inception_kernel, dim3(gx, gy), dim3(IT), 0, stream, x, y, planes, C, H, W, OH, OW,
+                       (float)H / (float)OH, (float)W / (float)OW, mul, add, 1.f / (255.f * std), -mean / std,
+                       gz::make_fastdiv((uint32_t)OW));
     return launch_status();
 }
 

@@ -202,11 +202,7 @@ int gz_upsample2_bwd(const float* gy, float* gx, long long planes, int H, int W,
 // written per element) instead of on the host.  One thread per output pixel, all channels.
 // ---------------------------------------------------------------------------
 namespace gz {
-// the one expression of the input step: (x / 255 - mean) / std as x * scale + shift.  Both kernels below call it, so
-// the compiler contracts (or does not contract) the multiply-add the same way in both and their results agree bit
-// for bit.
-__device__ __forceinline__ float u8_norm(unsigned char v, float scale, float shift) { return (float)v * scale + shift; }
-
+// (the one expression of the input step, u8_norm, lives in gz_common.h: gz_infer.hip's fused input kernel calls it too)
 __global__ __launch_bounds__(256) void u8hwc_to_nchw_kernel(const unsigned char* __restrict__ in,
                                                             float* __restrict__ out, long long pixels, int HW, int C,
                                                             float scale, float shift, FastDiv div_hw) {

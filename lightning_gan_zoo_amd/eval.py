@@ -13,6 +13,11 @@ SURVEY.md 8-f3) minus the Inception network itself, whose weights are fetched fr
 The arithmetic is pinned to the reference's own functions by tests/golden/eval_metrics.npz
 (tests/golden/make_eval_golden.py).  Host-side numpy / scipy like the reference; only the generator runs on the GPU -- and, opt-in
 (``kid_on_device``), KID's kernel-matrix sums (``polynomial_mmd_averages_device``, csrc/gz_kid.hip).
+
+``evaluate_device`` is the same evaluation with the activations resident on the GPU from the generator to the two small
+results that leave it: ``SampleDump.device_batches`` (generator output -> Inception input in one launch,
+gz_samples_to_inception_input), the network at a large batch, fp64 mean / covariance (``feature_moments_device``,
+csrc/gz_moments.hip) and KID's sums.  The matrix square root stays on the host.
 """
 import numpy as np
 import torch
@@ -37,6 +42,39 @@ class SampleDump:
                 samples = torch.clamp(samples, 0, 1)          # sic: the tanh output is clamped, not de-normalised (:197)
                 samples = samples.permute(0, 2, 3, 1).detach().cpu().numpy()
                 yield (samples * 255).astype(int).astype(np.uint8)
+        finally:
+            module.train(was_training)
+
+    @torch.no_grad()
+    def device_batches(self, module, batch=250, size=(299, 299), mul=2.0, add=-1.0):
+        """Yields float32 device tensors [b, 3, size[0], size[1]]: the images of ``images`` as InceptionV3 reads them --
+        clamp, grey level, ToTensor, bilinear resize, ``* mul + add`` -- made from the generator's output by one launch
+        (gz_samples_to_inception_input), bit-equal to ``images`` -> ``functional.normalize_u8_images(u8, 0, 1)`` ->
+        gz_resize_bilinear.  Eval mode under no_grad, mode restored afterwards.  A generator that draws on the host in
+        every call (``sample_view``: HoloGAN's view, from numpy's global generator) is called on the dump's own splits,
+        so numpy's stream is left exactly as ``images`` leaves it; any other generator is called on ``batch`` latents
+        at a time.  No CPU fallback."""
+        from . import functional as F
+        from ._lib import check, lib
+        if torch.device(module.device).type != "cuda":
+            raise RuntimeError("lightning_gan_zoo_amd.eval: the device evaluation pass runs on the HIP kernels; device %r "
+                               "is not a GPU and there is no fallback (use SampleDump.images)" % (module.device,))
+        OH, OW = int(size[0]), int(size[1])
+        if hasattr(module.generator, "sample_view"):
+            splits = self.z_samples
+        else:
+            splits = torch.split(torch.cat(list(self.z_samples)), int(batch))
+        was_training = module.training
+        module.eval()
+        try:
+            for z in splits:
+                samples = F._req(module.generator(z.to(module.device)).detach().float(), "samples")
+                N, C, H, W = samples.shape
+                y = torch.empty((N, 3, OH, OW), device=samples.device, dtype=torch.float32)
+                with torch.cuda.device(samples.device):
+                    check(lib.gz_samples_to_inception_input(F._p(samples), F._p(y), N, C, H, W, OH, OW, float(mul),
+                                                            float(add), F._stream()), "samples_to_inception_input")
+                yield y
         finally:
             module.train(was_training)
 
@@ -276,6 +314,69 @@ def polynomial_mmd_averages_device(codes_g, codes_r, n_subsets=50, subset_size=1
     idx = draw_kid_subsets(g.shape[0], r.shape[0], n_subsets, subset_size)
     sums = kid_sums_device(g, r, idx, degree=degree, gamma=gamma, coef0=coef0)
     return _mmd2_and_variance_from_sums(sums, idx.shape[2], var_at_m=min(g.shape[0], r.shape[0]), ret_var=ret_var)
+
+
+def feature_moments_device(codes):
+    """(mean [d], cov [d, d]) of fp64 device codes [n, d] as fp64 device tensors: ``np.mean(codes, axis=0)`` and
+    ``np.cov(codes, rowvar=False)`` in numpy's two-pass form on the fp64 MFMA kernel (gz_feature_moments,
+    csrc/gz_moments.hip).  Deterministic, cov bitwise symmetric.  No CPU fallback."""
+    from . import functional as F
+    from ._lib import check, lib
+    if not isinstance(codes, torch.Tensor) or codes.dim() != 2 or codes.dtype != torch.float64:
+        raise ValueError("codes must be a float64 [n, d] tensor (eval.device_codes makes one)")
+    if not codes.is_cuda:
+        raise RuntimeError("lightning_gan_zoo_amd.eval: the device moments run on the HIP kernels; device %r is not a GPU "
+                           "and there is no fallback (use activation_statistics)" % (codes.device,))
+    codes = codes if codes.is_contiguous() else codes.contiguous()
+    n, d = codes.shape
+    with torch.cuda.device(codes.device):
+        mean = torch.empty((d,), dtype=torch.float64, device=codes.device)
+        cov = torch.empty((d, d), dtype=torch.float64, device=codes.device)
+        ws_bytes = lib.gz_feature_moments_workspace_bytes(n, d)
+        ws = torch.empty(max(ws_bytes, 8), dtype=torch.uint8, device=codes.device)
+        check(lib.gz_feature_moments(F._p(codes), n, d, F._p(mean), F._p(cov), F._p(ws), ws_bytes, F._stream()),
+              "feature_moments")
+    return mean, cov
+
+
+class RealStatistics:
+    """What ``evaluate_device`` reads of the real set, made ONCE per run (the set does not change between epochs): its
+    fp64 codes resident on the device (KID draws its subsets from them) and their mean and covariance on the host
+    (``frechet_distance``'s operands).  ``mu`` / ``sigma``: statistics already known (an ``inception_cache.npz``);
+    without them one gz_feature_moments call."""
+
+    def __init__(self, real_act, device, mu=None, sigma=None):
+        self.codes = device_codes(real_act, device)
+        if mu is None or sigma is None:
+            mean, cov = feature_moments_device(self.codes)
+            mu, sigma = mean.cpu().numpy(), cov.cpu().numpy()
+        self.mu, self.sigma = np.asarray(mu, dtype=np.float64), np.asarray(sigma, dtype=np.float64)
+
+
+def device_activations(module, dump, net, batch=250):
+    """The generated set's features as fp64 rows of ONE resident [n, d] device tensor (fp32 -> fp64 is exact).  ``net``:
+    Inception inputs [b, 3, 299, 299] on the device -> features [b, d] on the device (``InceptionFeatures.device``)."""
+    act, row = None, 0
+    for x in dump.device_batches(module, batch):
+        f = net(x)
+        if act is None:
+            act = torch.empty((dump.n_samples, f.shape[1]), dtype=torch.float64, device=f.device)
+        act[row:row + f.shape[0]].copy_(f)
+        row += f.shape[0]
+    assert row == dump.n_samples
+    return act
+
+
+def evaluate_device(module, dump, net, real, batch=250, n_subsets=100):
+    """``evaluate`` with everything between the generator and the metrics on the device: features at batch ``batch``
+    into one resident fp64 tensor, mean / covariance through gz_feature_moments (only those two are copied to the host,
+    for ``frechet_distance``), KID through ``polynomial_mmd_averages_device`` on the resident tensors -- the same subset
+    draws from numpy's global generator.  ``real``: a ``RealStatistics``.  Returns the same dict as ``evaluate``."""
+    fake = device_activations(module, dump, net, batch)
+    mean, cov = feature_moments_device(fake)
+    fid = frechet_distance(real.mu, real.sigma, mean.cpu().numpy(), cov.cpu().numpy())
+    kid = polynomial_mmd_averages_device(real.codes, fake, n_subsets=n_subsets, device=fake.device)
+    return {"fid": fid, "kid": float(kid[0].mean()), "kid_std": float(kid[0].std())}
 
 
 def evaluate(module, dump, feature_fn, real_act, n_subsets=100, kid_on_device=False, real_codes_device=None):

@@ -289,12 +289,17 @@ class InceptionFeatures:
 
     def __init__(self, net, batch_size=16):
         self.net, self.batch_size = net, batch_size
-        self.device = next(net.parameters()).device
+        self._device = next(net.parameters()).device
 
     def __call__(self, images_u8):
         out = []
         for i in range(0, len(images_u8), self.batch_size):
-            u8 = torch.from_numpy(np.ascontiguousarray(images_u8[i:i + self.batch_size])).to(self.device)
+            u8 = torch.from_numpy(np.ascontiguousarray(images_u8[i:i + self.batch_size])).to(self._device)
             x = F.normalize_u8_images(u8, 0.0, 1.0)            # ToTensor: [n, 3, H, W] in [0, 1]
             out.append(self.net(x).double().cpu().numpy())
         return np.concatenate(out, axis=0)
+
+    def device(self, x_inputs):
+        """The network on inputs that are already resized and normalised ([b, 3, 299, 299] float32 on the device, what
+        ``eval.SampleDump.device_batches`` yields) -> features [b, 2048] float32, left on the device."""
+        return self.net(x_inputs, resize_input=False, normalize_input=False)

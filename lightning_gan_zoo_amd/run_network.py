@@ -45,7 +45,11 @@ RUNNER_KEYS = {"max_steps": None, "log_every": 10, "dataset_path": None, "seed":
                "generator_average": False, "generator_average_beta": 0.999,
                # KID's kernel-matrix sums on the GPU (eval.polynomial_mmd_averages_device, csrc/gz_kid.hip) instead of
                # ~a minute of host fp64 GEMMs per evaluation; FID stays on the host
-               "kid_on_device": False}
+               "kid_on_device": False,
+               # the whole evaluation pass on the device (eval.evaluate_device): generator and InceptionV3 at
+               # eval_batch_size, activations resident in fp64, mean / covariance on csrc/gz_moments.hip, KID as with
+               # kid_on_device (implied); only the matrix square root of the Frechet distance stays on the host
+               "eval_on_device": False, "eval_batch_size": 250}
 BUILTIN_DATASETS = ("synthetic", "image_folder", "tensor_file", "celeb_a", "mnist")
 AVERAGE_PREFIX = "generator_average."     # state_dict keys of the averaged generator's parameters, next to generator.*
 LIGHTNING_VERSION_TAG = "1.2.0"       # envelope layout written below (Lightning 1.1 / 1.2 generation)
@@ -640,6 +644,18 @@ def real_image_files(root):
     return sorted(out)
 
 
+def real_statistics_cache(root):
+    """(mu, sigma) of the real set as ``real_activations`` persisted them (``<root>/inception_cache.npz``), or
+    (None, None) without that file."""
+    path = os.path.join(root, "inception_cache.npz")
+    if not os.path.exists(path):
+        return None, None
+    with np.load(path) as data:
+        if "mu" not in data or "sigma" not in data:
+            return None, None
+        return np.asarray(data["mu"]), np.asarray(data["sigma"])
+
+
 def real_activations(root, features, batch_size=16):
     """Inception activations of the real images as the reference's callback obtains them (:159-163, :211-221): the
     first ``*.npz`` in ``root`` if there is one (keys mu / sigma / act), else every image at its NATIVE resolution --
@@ -683,6 +699,22 @@ def wants_fid(cfg, run):
                 and str(node.get("_target_", "")).endswith("ImageFolder"))
 
 
+def device_fid_evaluator(dump, features, real_act, device, batch=250, average=None, mu=None, sigma=None):
+    """The ``evaluate`` hook of fit() on the device pass (eval.evaluate_device).  The real set's device codes and its
+    mean / covariance (``mu`` / ``sigma`` when a cache file holds them, else one moments launch) are made here, once per
+    run; every epoch then costs the generated set alone."""
+    from . import eval as E
+    real = E.RealStatistics(real_act, device, mu=mu, sigma=sigma)
+
+    def evaluate(mod, epoch):
+        with rendering_from(mod, average):          # generator_average=true: the averaged generator is what is scored
+            m = E.evaluate_device(mod, dump, features.device, real, batch=batch)
+        print("epoch %d FID: %.4f KID mean: %.6f KID stddev: %.6f" % (epoch, m["fid"], m["kid"], m["kid_std"]))
+        return m
+
+    return evaluate
+
+
 def make_fid_evaluator(cfg, run, module, device, average=None):
     """The reference's InceptionMetrics callback (run_network.py:51-56, core/callback_inception_metrics.py:136-246) as
     the ``evaluate`` hook of fit(): FID / KID of ``val.fid_n_samples`` generated images against the validation images,
@@ -706,6 +738,10 @@ def make_fid_evaluator(cfg, run, module, device, average=None):
     # parallelism the other ranks wait for it ONCE, at start-up (main() gives the process group a long timeout), not
     # inside a collective in the middle of the run
     real_act = real_activations(val_root, features)
+    if run.get("eval_on_device", False):
+        mu, sigma = real_statistics_cache(val_root)
+        return device_fid_evaluator(dump, features, real_act, device, batch=int(run.get("eval_batch_size", 250)),
+                                    average=average, mu=mu, sigma=sigma)
     kid_on_device = bool(run.get("kid_on_device", False))
     # real_act is the same every epoch: its fp64 device copy is made once per run, here
     real_codes = E.device_codes(real_act, device) if kid_on_device else None
