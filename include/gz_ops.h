@@ -587,6 +587,28 @@ size_t gz_feature_moments_workspace_bytes(long long n, int d);
 int gz_feature_moments(const double* act, long long n, int d, double* mean, double* cov, void* workspace,
                        size_t ws_bytes, hipStream_t stream);
 
+/* ---- matrix square root on the device: the Newton-Schulz primitives (csrc/gz_sqrtm.hip) --------------
+ * gz_sqrtm_product: C = alpha * (A B) + beta * I for fp64 row-major d x d DEVICE matrices on v_mfma_f64_16x16x4_f64, one
+ * workgroup per 64 x 64 tile of C with the whole reduction index inside it.  Nothing is assumed about symmetry; d needs
+ * no multiple of anything (indices >= d are never dereferenced).  C must not overlap A or B; A and B may be one matrix.
+ * gz_sqrtm_product_pair: two such products of one size in ONE launch (the iteration's Y T and T Z), each with its own
+ * operands and coefficients; neither output may overlap any of the four operands or the other output.
+ * Deterministic: no floating-point atomics, every entry summed over k in k order, C is written and never read; two calls
+ * give equal bits.  No workspace.  The launcher neither synchronises nor allocates: one launch on `stream`.
+ * GZ_ERR_BAD_SHAPE: d < 1, a null pointer, an output that overlaps an operand or the other output (nothing is launched).
+ *
+ * gz_sqrtm_trace_norm: out[0] = trace(A), out[1] = |A|_F^2 (the sum of the squared entries) of a d x d DEVICE matrix into
+ * two DEVICE doubles, in a fixed order: 8 rows per workgroup into the workspace (gz_sqrtm_trace_norm_workspace_bytes
+ * bytes, never read before it is written), then the workgroups' shares in workgroup order.  Two launches on `stream`.
+ * GZ_ERR_BAD_SHAPE: d < 1, a null pointer; GZ_ERR_WORKSPACE: workspace too short (nothing is launched). */
+int gz_sqrtm_product(const double* a, const double* b, double* c, int d, double alpha, double beta,
+                     hipStream_t stream);
+int gz_sqrtm_product_pair(const double* a0, const double* b0, double* c0, double alpha0, double beta0,
+                          const double* a1, const double* b1, double* c1, double alpha1, double beta1, int d,
+                          hipStream_t stream);
+size_t gz_sqrtm_trace_norm_workspace_bytes(int d);
+int gz_sqrtm_trace_norm(const double* a, int d, double* out, void* workspace, size_t ws_bytes, hipStream_t stream);
+
 /* text of the last HIP error seen by a launcher on the calling thread ("" if none) */
 const char* gz_last_error(void);
 

@@ -17,7 +17,9 @@ The arithmetic is pinned to the reference's own functions by tests/golden/eval_m
 ``evaluate_device`` is the same evaluation with the activations resident on the GPU from the generator to the two small
 results that leave it: ``SampleDump.device_batches`` (generator output -> Inception input in one launch,
 gz_samples_to_inception_input), the network at a large batch, fp64 mean / covariance (``feature_moments_device``,
-csrc/gz_moments.hip) and KID's sums.  The matrix square root stays on the host.
+csrc/gz_moments.hip) and KID's sums.  The matrix square root stays on the host unless ``fid_on_device`` asks for
+``frechet_distance_device``: two Newton-Schulz square roots of symmetric positive semi-definite matrices, matrix products
+alone, on the fp64 MFMA product of csrc/gz_sqrtm.hip.  ``frechet_distance_newton_schulz`` is the same recurrence in numpy.
 """
 import numpy as np
 import torch
@@ -134,6 +136,76 @@ def frechet_distance(mu1, sigma1, mu2, sigma2, eps=1e-6):
             return float("nan")
         root = root.real
     return float(delta.dot(delta) + np.trace(sigma1) + np.trace(sigma2) - 2 * np.trace(root))
+
+
+NS_MAXIT = 100          # iterations after which a Newton-Schulz root counts as not converged
+NS_TOL = 1e-14          # the trace moved by no more than this, relatively: converged
+NS_FLOOR = 1e-10        # the trace's movement stopped shrinking below this: the rounding floor, keep the iterate before
+
+
+def _ns_verdict(t, tn, dprev):
+    """The stop rule of the coupled Newton-Schulz iteration from the traces of two successive iterates ->
+    (verdict, |tn - t|): "fail" (not finite), "new" (converged, take the new iterate), "old" (the rounding floor is
+    reached: on a rank-deficient matrix the noise in the null space grows from here on, take the iterate before) or
+    "go".  One function for the numpy restatement and the device loop."""
+    dk = abs(tn - t)
+    if not np.isfinite(tn):
+        return "fail", dk
+    if dk <= NS_TOL * abs(tn):
+        return "new", dk
+    if dk >= dprev and dk <= NS_FLOOR * abs(tn):
+        return "old", dk
+    return "go", dk
+
+
+def _newton_schulz(a, maxit=NS_MAXIT):
+    """Coupled Newton-Schulz iteration for the square root of a symmetric positive semi-definite matrix, plain products,
+    nothing symmetrised: Y0 = A / c, Z0 = I, T = 1.5 I - 0.5 Z Y, Y <- Y T, Z <- T Z with c = |A|_F, so that
+    sqrt(A) ~ sqrt(c) Y.  -> (Y, c, trace(Y), iterations, converged)."""
+    a = np.atleast_2d(np.asarray(a, dtype=np.float64))
+    d = a.shape[0]
+    c = float(np.sqrt(np.sum(a * a)))
+    if c == 0.0:
+        return np.zeros_like(a), 0.0, 0.0, 0, True
+    if not np.isfinite(c):
+        return a, c, float("nan"), 0, False
+    eye = np.eye(d)
+    y, z = a / c, eye.copy()
+    t, dprev = float(np.trace(y)), float("inf")
+    for k in range(1, int(maxit) + 1):
+        tk = 1.5 * eye - 0.5 * z.dot(y)
+        yn, z = y.dot(tk), tk.dot(z)
+        tn = float(np.trace(yn))
+        verdict, dk = _ns_verdict(t, tn, dprev)
+        if verdict == "fail":
+            return y, c, t, k, False
+        if verdict == "new":
+            return yn, c, tn, k, True
+        if verdict == "old":
+            return y, c, t, k, True
+        y, t, dprev = yn, tn, dk
+    return y, c, t, int(maxit), False
+
+
+def sqrtm_psd_newton_schulz(a, maxit=NS_MAXIT):
+    """-> (root, iterations, converged) of a symmetric positive semi-definite matrix (``_newton_schulz``)."""
+    y, c, _, k, ok = _newton_schulz(a, maxit)
+    return np.sqrt(c) * y, k, ok
+
+
+def frechet_distance_newton_schulz(mu1, sigma1, mu2, sigma2, maxit=NS_MAXIT):
+    """The Frechet distance with Tr (S1 S2)^(1/2) = Tr (R S2 R)^(1/2), R = S1^(1/2): two roots of symmetric positive
+    semi-definite matrices by ``_newton_schulz``.  The CPU restatement of ``frechet_distance_device``.
+    -> (distance, (iterations of R, iterations of the second root), converged: both did)."""
+    mu1, mu2 = np.atleast_1d(mu1), np.atleast_1d(mu2)
+    sigma1, sigma2 = np.atleast_2d(sigma1), np.atleast_2d(sigma2)
+    if mu1.shape != mu2.shape or sigma1.shape != sigma2.shape:
+        raise ValueError("the two statistics have different dimensions")
+    delta = mu1 - mu2
+    root1, k1, ok1 = sqrtm_psd_newton_schulz(sigma1, maxit)
+    _, c, t, k2, ok2 = _newton_schulz(root1.dot(sigma2).dot(root1), maxit)
+    fid = float(delta.dot(delta) + np.trace(sigma1) + np.trace(sigma2) - 2 * (np.sqrt(c) * t))
+    return fid, (k1, k2), bool(ok1 and ok2)
 
 
 def _poly_kernel(x, y, degree, gamma, coef0):
@@ -339,11 +411,121 @@ def feature_moments_device(codes):
     return mean, cov
 
 
+def _square_fp64_device(a, what):
+    if not isinstance(a, torch.Tensor) or a.dim() != 2 or a.shape[0] != a.shape[1] or a.dtype != torch.float64:
+        raise ValueError("%s must be a square float64 tensor" % what)
+    if not a.is_cuda:
+        raise RuntimeError("lightning_gan_zoo_amd.eval: the device square root runs on the HIP kernels; device %r is not a "
+                           "GPU and there is no fallback (use frechet_distance)" % (a.device,))
+    return a if a.is_contiguous() else a.contiguous()
+
+
+class _SqrtmLaunchers:
+    """The launchers of csrc/gz_sqrtm.hip for d x d matrices on one device, with the reduction's workspace and its two
+    result doubles allocated once."""
+
+    def __init__(self, d, device):
+        from . import functional as F
+        from ._lib import check, lib
+        self.F, self.check, self.lib, self.d = F, check, lib, int(d)
+        self.ws_bytes = lib.gz_sqrtm_trace_norm_workspace_bytes(self.d)
+        self.ws = torch.empty(max(self.ws_bytes, 8), dtype=torch.uint8, device=device)
+        self.stats = torch.empty(2, dtype=torch.float64, device=device)
+
+    def product(self, a, b, c, alpha=1.0, beta=0.0):
+        p = self.F._p
+        self.check(self.lib.gz_sqrtm_product(p(a), p(b), p(c), self.d, float(alpha), float(beta), self.F._stream()),
+                   "sqrtm_product")
+
+    def product_pair(self, a0, b0, c0, a1, b1, c1):
+        p = self.F._p
+        self.check(self.lib.gz_sqrtm_product_pair(p(a0), p(b0), p(c0), 1.0, 0.0, p(a1), p(b1), p(c1), 1.0, 0.0, self.d,
+                                                  self.F._stream()), "sqrtm_product_pair")
+
+    def trace_norm(self, a):
+        """(trace(a), |a|_F^2) on the host: two launches and the 16-byte read-back."""
+        p = self.F._p
+        self.check(self.lib.gz_sqrtm_trace_norm(p(a), self.d, p(self.stats), p(self.ws), self.ws_bytes,
+                                                self.F._stream()), "sqrtm_trace_norm")
+        tr, f2 = self.stats.tolist()
+        return tr, f2
+
+
+def _newton_schulz_device(a, launch, maxit=NS_MAXIT):
+    """``_newton_schulz`` on the device: the loop runs here over the launchers, three products (two of them in one
+    launch) and one 16-byte read-back per iteration; five d x d work buffers allocated once.
+    -> (Y: one of the work buffers, c, trace(Y), iterations, converged)."""
+    d = a.shape[0]
+    _, f2 = launch.trace_norm(a)
+    c = float(np.sqrt(f2))
+    if c == 0.0:
+        return torch.zeros_like(a), 0.0, 0.0, 0, True
+    if not np.isfinite(c):
+        return a, c, float("nan"), 0, False
+    y, z, tk, yn, zn = torch.empty((5, d, d), dtype=torch.float64, device=a.device).unbind(0)
+    torch.div(a, c, out=y)
+    z.zero_()
+    z.diagonal().fill_(1.0)
+    t, dprev = launch.trace_norm(y)[0], float("inf")
+    for k in range(1, int(maxit) + 1):
+        launch.product(z, y, tk, -0.5, 1.5)
+        launch.product_pair(y, tk, yn, tk, z, zn)
+        tn = launch.trace_norm(yn)[0]
+        verdict, dk = _ns_verdict(t, tn, dprev)
+        if verdict == "fail":
+            return y, c, t, k, False
+        if verdict == "new":
+            return yn, c, tn, k, True
+        if verdict == "old":
+            return y, c, t, k, True
+        y, yn, z, zn, t, dprev = yn, y, zn, z, tn, dk
+    return y, c, t, int(maxit), False
+
+
+def sqrtm_psd_device(a, maxit=NS_MAXIT):
+    """The square root of a symmetric positive semi-definite fp64 device matrix by the coupled Newton-Schulz iteration
+    on gz_sqrtm_product (csrc/gz_sqrtm.hip) -> (root: a device tensor of its own, iterations, converged).  No CPU
+    fallback."""
+    a = _square_fp64_device(a, "a")
+    with torch.cuda.device(a.device):
+        y, c, _, k, ok = _newton_schulz_device(a, _SqrtmLaunchers(a.shape[0], a.device), maxit)
+        return y * float(np.sqrt(c)), k, ok
+
+
+def frechet_distance_device(mu1, sigma1, mu2, sigma2, root1=None, maxit=NS_MAXIT):
+    """``frechet_distance_newton_schulz`` on fp64 device statistics (``feature_moments_device`` makes them).  ``root1``:
+    the square root of ``sigma1`` from an earlier ``sqrtm_psd_device`` call (the real set's does not change between
+    epochs); its iteration count is then reported as 0.  -> (distance, (iterations, iterations), converged).  No CPU
+    fallback."""
+    sigma1, sigma2 = _square_fp64_device(sigma1, "sigma1"), _square_fp64_device(sigma2, "sigma2")
+    d = sigma1.shape[0]
+    for m in (mu1, mu2):
+        if not isinstance(m, torch.Tensor) or m.dtype != torch.float64 or tuple(m.shape) != (d,):
+            raise ValueError("the means must be float64 [%d] tensors" % d)
+    if sigma2.shape != sigma1.shape:
+        raise ValueError("the two statistics have different dimensions")
+    with torch.cuda.device(sigma1.device):
+        launch = _SqrtmLaunchers(d, sigma1.device)
+        k1, ok1 = 0, True
+        if root1 is None:
+            root1, k1, ok1 = sqrtm_psd_device(sigma1, maxit)
+        root1 = _square_fp64_device(root1, "root1")
+        half, inner = torch.empty((2, d, d), dtype=torch.float64, device=sigma1.device).unbind(0)
+        launch.product(root1, sigma2, half)
+        launch.product(half, root1, inner)
+        _, c, t, k2, ok2 = _newton_schulz_device(inner, launch, maxit)
+        delta = (mu1 - mu2.to(mu1.device)).cpu().numpy()
+        tr1, tr2 = launch.trace_norm(sigma1)[0], launch.trace_norm(sigma2)[0]
+        fid = float(delta.dot(delta) + tr1 + tr2 - 2 * (np.sqrt(c) * t))
+    return fid, (k1, k2), bool(ok1 and ok2)
+
+
 class RealStatistics:
     """What ``evaluate_device`` reads of the real set, made ONCE per run (the set does not change between epochs): its
     fp64 codes resident on the device (KID draws its subsets from them) and their mean and covariance on the host
     (``frechet_distance``'s operands).  ``mu`` / ``sigma``: statistics already known (an ``inception_cache.npz``);
-    without them one gz_feature_moments call."""
+    without them one gz_feature_moments call.  ``device_root`` (``fid_on_device``): the statistics as device tensors and
+    the square root of ``sigma``, made on first use and kept."""
 
     def __init__(self, real_act, device, mu=None, sigma=None):
         self.codes = device_codes(real_act, device)
@@ -351,6 +533,17 @@ class RealStatistics:
             mean, cov = feature_moments_device(self.codes)
             mu, sigma = mean.cpu().numpy(), cov.cpu().numpy()
         self.mu, self.sigma = np.asarray(mu, dtype=np.float64), np.asarray(sigma, dtype=np.float64)
+        self._root = None
+
+    def device_root(self):
+        """-> (mu, sigma, root of sigma: fp64 device tensors, iterations, converged); one ``sqrtm_psd_device`` call per
+        run."""
+        if self._root is None:
+            dev = self.codes.device
+            mu = torch.from_numpy(np.ascontiguousarray(self.mu)).to(dev)
+            sigma = torch.from_numpy(np.ascontiguousarray(np.atleast_2d(self.sigma))).to(dev)
+            self._root = (mu, sigma) + tuple(sqrtm_psd_device(sigma))
+        return self._root
 
 
 def device_activations(module, dump, net, batch=250):
@@ -367,14 +560,38 @@ def device_activations(module, dump, net, batch=250):
     return act
 
 
-def evaluate_device(module, dump, net, real, batch=250, n_subsets=100):
+_fid_fallback_warned = False
+
+
+def _fid_on_device(real, mean, cov):
+    """The device Frechet distance with the real set's cached root; an iteration that does not converge sends THIS
+    evaluation to the host's ``frechet_distance`` on the same moments (warned about once per run)."""
+    global _fid_fallback_warned
+    mu1, sigma1, root1, _, ok = real.device_root()
+    if ok:
+        fid, _, ok = frechet_distance_device(mu1, sigma1, mean, cov, root1=root1)
+    if not ok:
+        if not _fid_fallback_warned:
+            _fid_fallback_warned = True
+            import warnings
+            warnings.warn("lightning_gan_zoo_amd.eval: the Newton-Schulz square root did not converge within %d iterations; "
+                          "the Frechet distance of this evaluation comes from the host (scipy.linalg.sqrtm)" % NS_MAXIT)
+        fid = frechet_distance(real.mu, real.sigma, mean.cpu().numpy(), cov.cpu().numpy())
+    return fid
+
+
+def evaluate_device(module, dump, net, real, batch=250, n_subsets=100, fid_on_device=False):
     """``evaluate`` with everything between the generator and the metrics on the device: features at batch ``batch``
     into one resident fp64 tensor, mean / covariance through gz_feature_moments (only those two are copied to the host,
     for ``frechet_distance``), KID through ``polynomial_mmd_averages_device`` on the resident tensors -- the same subset
-    draws from numpy's global generator.  ``real``: a ``RealStatistics``.  Returns the same dict as ``evaluate``."""
+    draws from numpy's global generator.  ``real``: a ``RealStatistics``.  ``fid_on_device``: the moments stay on the
+    device and ``frechet_distance_device`` runs with the real set's cached root.  Returns the same dict as ``evaluate``."""
     fake = device_activations(module, dump, net, batch)
     mean, cov = feature_moments_device(fake)
-    fid = frechet_distance(real.mu, real.sigma, mean.cpu().numpy(), cov.cpu().numpy())
+    if fid_on_device:
+        fid = _fid_on_device(real, mean, cov)
+    else:
+        fid = frechet_distance(real.mu, real.sigma, mean.cpu().numpy(), cov.cpu().numpy())
     kid = polynomial_mmd_averages_device(real.codes, fake, n_subsets=n_subsets, device=fake.device)
     return {"fid": fid, "kid": float(kid[0].mean()), "kid_std": float(kid[0].std())}
 

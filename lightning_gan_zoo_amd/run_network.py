@@ -49,7 +49,11 @@ RUNNER_KEYS = {"max_steps": None, "log_every": 10, "dataset_path": None, "seed":
                # the whole evaluation pass on the device (eval.evaluate_device): generator and InceptionV3 at
                # eval_batch_size, activations resident in fp64, mean / covariance on csrc/gz_moments.hip, KID as with
                # kid_on_device (implied); only the matrix square root of the Frechet distance stays on the host
-               "eval_on_device": False, "eval_batch_size": 250}
+               "eval_on_device": False, "eval_batch_size": 250,
+               # with eval_on_device: the Frechet distance's matrix square roots on the device too (Newton-Schulz on
+               # csrc/gz_sqrtm.hip, eval.frechet_distance_device); within 1e-9 (rank-deficient statistics: 1e-7) of
+               # tr S1 + tr S2 of the host value, which an evaluation whose iteration does not converge falls back to
+               "fid_on_device": False}
 BUILTIN_DATASETS = ("synthetic", "image_folder", "tensor_file", "celeb_a", "mnist")
 AVERAGE_PREFIX = "generator_average."     # state_dict keys of the averaged generator's parameters, next to generator.*
 LIGHTNING_VERSION_TAG = "1.2.0"       # envelope layout written below (Lightning 1.1 / 1.2 generation)
@@ -81,7 +85,14 @@ def parse_overrides(argv):
     expt = next((parse_value(a.split("=", 1)[1]) for a in rest if a.split("=", 1)[0] in ("+expt", "expt")), None)
     if expt is None:
         raise SystemExit("missing +expt=<dc_gan|wgan|wgan_gp|hologan|gan_stability_r1>")
+    check_eval_keys(runner)
     return conf_dir, expt, rest, runner
+
+
+def check_eval_keys(run):
+    if run.get("fid_on_device", False) and not run.get("eval_on_device", False):
+        raise SystemExit("fid_on_device=true is honoured only together with eval_on_device=true: the device Frechet "
+                         "distance reads the moments the device evaluation pass leaves on the GPU")
 
 
 def _builtin_dataset(name, run, filepaths):
@@ -699,16 +710,19 @@ def wants_fid(cfg, run):
                 and str(node.get("_target_", "")).endswith("ImageFolder"))
 
 
-def device_fid_evaluator(dump, features, real_act, device, batch=250, average=None, mu=None, sigma=None):
+def device_fid_evaluator(dump, features, real_act, device, batch=250, average=None, mu=None, sigma=None,
+                         fid_on_device=False):
     """The ``evaluate`` hook of fit() on the device pass (eval.evaluate_device).  The real set's device codes and its
     mean / covariance (``mu`` / ``sigma`` when a cache file holds them, else one moments launch) are made here, once per
-    run; every epoch then costs the generated set alone."""
+    run; every epoch then costs the generated set alone.  ``fid_on_device``: the Frechet distance on the device as well
+    (the real covariance's square root is made by the first evaluation and kept)."""
     from . import eval as E
     real = E.RealStatistics(real_act, device, mu=mu, sigma=sigma)
+    extra = {"fid_on_device": True} if fid_on_device else {}
 
     def evaluate(mod, epoch):
         with rendering_from(mod, average):          # generator_average=true: the averaged generator is what is scored
-            m = E.evaluate_device(mod, dump, features.device, real, batch=batch)
+            m = E.evaluate_device(mod, dump, features.device, real, batch=batch, **extra)
         print("epoch %d FID: %.4f KID mean: %.6f KID stddev: %.6f" % (epoch, m["fid"], m["kid"], m["kid_std"]))
         return m
 
@@ -728,6 +742,7 @@ def make_fid_evaluator(cfg, run, module, device, average=None):
     val_root = (node.get("val") or {}).get("root")
     if not val_root or not str(node.get("_target_", "")).endswith("ImageFolder"):
         return None
+    check_eval_keys(run)
     from . import eval as E
     from .inception import InceptionFeatures, load_fid_weights
     features = InceptionFeatures(load_fid_weights(run["inception_weights"], device,
@@ -741,7 +756,8 @@ def make_fid_evaluator(cfg, run, module, device, average=None):
     if run.get("eval_on_device", False):
         mu, sigma = real_statistics_cache(val_root)
         return device_fid_evaluator(dump, features, real_act, device, batch=int(run.get("eval_batch_size", 250)),
-                                    average=average, mu=mu, sigma=sigma)
+                                    average=average, mu=mu, sigma=sigma,
+                                    fid_on_device=bool(run.get("fid_on_device", False)))
     kid_on_device = bool(run.get("kid_on_device", False))
     # real_act is the same every epoch: its fp64 device copy is made once per run, here
     real_codes = E.device_codes(real_act, device) if kid_on_device else None

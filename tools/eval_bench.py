@@ -12,7 +12,14 @@ Per sample count n the one JSON line holds
   * ``evaluate_device_s``  eval.evaluate_device: batch ``--batch``, activations resident, gz_feature_moments, the same KID,
                            the same host sqrtm;
   * ``device_features_moments_s``  the part of it that bench.py's ``fid50k_features.seconds`` times, plus the moments;
-  * ``sqrtm_s``            eval.frechet_distance alone on the two statistics (host, in both paths);
+  * ``sqrtm_s``            eval.frechet_distance alone on the two statistics (host; ``fid_on_device=false``);
+  * ``fid_device_s``       eval.frechet_distance_device on the same statistics with the real set's cached root: what one
+                           epoch pays with ``fid_on_device=true``; ``root_real_s`` the once-per-run root of the real
+                           covariance; ``root_real_iterations`` / ``fid_device_iterations`` the Newton-Schulz iteration
+                           counts, ``fid_rel_diff`` = |device - host| / |host| of the two distances,
+                           ``sqrtm_over_fid_device`` = sqrtm_s / fid_device_s;
+  * ``product_ms`` / ``product_fp64_tflops`` / ``product_pair_fp64_tflops``  gz_sqrtm_product and gz_sqrtm_product_pair at
+                           d x d by HIP events (median of ``--reps`` after two warm-ups; FLOP = 2 d^3 per product);
   * ``moments_ms`` / ``moments_fp64_tflops`` / ``np_cov_s``  the moments launch sequence by HIP events (median of
                            ``--reps`` after two warm-ups; FLOP = 2 n d^2 / 2 * (1 + 1/tiles): the upper-triangle tiles the
                            kernel executes) beside numpy's np.cov of the same array;
@@ -103,6 +110,18 @@ def moments_record(codes, reps):
             else None}
 
 
+def product_record(d, reps):
+    a, b = torch.randn(d, d, dtype=torch.float64, device="cuda"), torch.randn(d, d, dtype=torch.float64, device="cuda")
+    c, c2 = torch.empty_like(a), torch.empty_like(a)
+    one = events_ms(lambda: check(lib.gz_sqrtm_product(F._p(a), F._p(b), F._p(c), d, -0.5, 1.5, F._stream()),
+                                  "sqrtm_product"), reps, 2)
+    two = events_ms(lambda: check(lib.gz_sqrtm_product_pair(F._p(a), F._p(b), F._p(c), 1.0, 0.0, F._p(b), F._p(a), F._p(c2),
+                                                            1.0, 0.0, d, F._stream()), "sqrtm_product_pair"), reps, 2)
+    flop = 2.0 * d ** 3
+    return {"product_ms": round(one, 3), "product_fp64_tflops": round(flop / one / 1e9, 2),
+            "product_pair_ms": round(two, 3), "product_pair_fp64_tflops": round(2 * flop / two / 1e9, 2)}
+
+
 def input_record():
     N, C, H, W, OH, OW = 250, 3, 64, 64, 299, 299
     x = torch.rand(N, C, H, W, device="cuda") * 1.4 - 0.2
@@ -164,8 +183,16 @@ def main():
                                                     n_subsets=a.subsets))
         run["evaluate_device_s"] = round(t_dev, 3)
         mean, cov = fake[1]
-        t_sq, _ = wall(lambda: E.frechet_distance(real.mu, real.sigma, mean.cpu().numpy(), cov.cpu().numpy()))
+        t_sq, fid_host = wall(lambda: E.frechet_distance(real.mu, real.sigma, mean.cpu().numpy(), cov.cpu().numpy()))
         run["sqrtm_s"] = round(t_sq, 3)
+        t_root, (mu1, sigma1, root1, k_real, ok_real) = wall(real.device_root)      # once per run
+        t_fd, (fid_dev, (_, k_fake), ok_fake) = wall(lambda: E.frechet_distance_device(mu1, sigma1, mean, cov, root1=root1))
+        run.update({"root_real_s": round(t_root, 3), "fid_device_s": round(t_fd, 3), "root_real_iterations": k_real,
+                    "fid_device_iterations": k_fake, "fid_device_converged": bool(ok_real and ok_fake),
+                    "fid_rel_diff": abs(fid_dev - fid_host) / abs(fid_host),
+                    "sqrtm_over_fid_device": round(t_sq / t_fd, 2)})
+        run.update(product_record(mean.shape[0], a.reps))
+        del mu1, sigma1, root1
         run.update(moments_record(fake[0], a.reps))
         del fake
         if n in a.host_n:
