@@ -4,47 +4,36 @@
 //     K_AB = (gamma * A B^T + coef0)^degree,   G = codes_g[idx[s][0]],   R = codes_r[idx[s][1]]      (rows gathered on load)
 //
 // One workgroup per (subset, product, band of 64 rows); the four products are GG, RR, GR and RG, the last one only for
-// its row sums, which are the column sums of K_GR.  The workgroup walks every 64-column tile of its band, so each row
-// sum, the band's diagonal and the band's share of the Frobenius sum finish inside it:
-//   * wave w owns rows 16w .. 16w+15 of the band and four 16x16 accumulators (the tile's 64 columns) on
-//     v_mfma_f64_16x16x4_f64, whose C/D layout is col = lane & 15, row = (lane >> 4) + 4 * reg;
+// its row sums, which are the column sums of K_GR.  The workgroup walks every 64-column tile of its band on the fp64
+// tile core (gz_f64_tile.h: both operands [row][feature] images, the blocked k-slot map), so each row sum, the band's
+// diagonal and the band's share of the Frobenius sum finish inside it:
 //   * a lane adds the entries it holds to its four row accumulators tile after tile, 16-column block after block; at
 //     the end the 16 lanes of a row are folded by an xor butterfly (8 after 4 after 2 after 1);
-//   * the Frobenius share is summed per lane in the same order, folded over the wave by the xor butterfly, over the four
-//     waves in wave order, and written to the workspace; a second, tiny launch adds the bands in band order.
+//   * the Frobenius share is summed per lane in the same order, folded over the workgroup in the core's fixed order and
+//     written to the workspace; a second, tiny launch adds the bands in band order.
 // No floating-point atomics, no dependence on the previous content of `out` or the workspace: two calls give equal bits.
-// Feature chunks of 32 travel global -> registers -> LDS one chunk ahead of the MFMAs; a lane's four MFMA k-slots of a
-// chunk are (lane >> 4) * 8 + step, the same on both operands, so a dot product is summed in a fixed, permuted order.
 // Tails: rows and columns >= m read row m-1 and are masked in the epilogue; features >= d are zero in LDS.
-#include "gz_common.h"
+#include "gz_f64_tile.h"
 #include "../../include/gz_ops.h"
 
 namespace gz {
 
-typedef double f64x4 __attribute__((ext_vector_type(4)));
-typedef double f64x2 __attribute__((ext_vector_type(2)));
-
-constexpr int KID_THREADS = 256;
-constexpr int KID_BAND = 64;                 // rows per workgroup = columns per tile
-constexpr int KID_KC = 32;                   // features per LDS chunk
-constexpr int KID_LD = KID_KC + 2;           // LDS row stride in doubles: 16-byte aligned rows, 16 rows span all banks
-constexpr int KID_LOADS = KID_BAND * KID_KC / KID_THREADS;      // doubles per thread, operand and chunk
-
-__device__ __forceinline__ void kid_fetch(const double* __restrict__ codes, const long long (&off)[KID_LOADS], int k,
-                                          int d, double (&v)[KID_LOADS]) {
+// features k of the thread's 8 gathered rows, zero from d on
+__device__ __forceinline__ void kid_fetch(const double* __restrict__ codes, const long long (&off)[F64_LOADS], int k,
+                                          int d, double (&v)[F64_LOADS]) {
 #pragma unroll
-    for (int i = 0; i < KID_LOADS; ++i) v[i] = k < d ? codes[off[i] + k] : 0.0;
+    for (int i = 0; i < F64_LOADS; ++i) v[i] = k < d ? codes[off[i] + k] : 0.0;
 }
 
-__global__ __launch_bounds__(KID_THREADS) void kid_band_kernel(const double* __restrict__ codes_g,
+__global__ __launch_bounds__(F64_THREADS) void kid_band_kernel(const double* __restrict__ codes_g,
                                                                const double* __restrict__ codes_r, int d,
                                                                const int* __restrict__ idx, int m, int nb, double gamma,
                                                                double coef0, int degree, double* __restrict__ out,
                                                                double* __restrict__ frob) {
-    __shared__ __attribute__((aligned(16))) double sA[KID_BAND * KID_LD];
-    __shared__ __attribute__((aligned(16))) double sB[KID_BAND * KID_LD];
-    __shared__ int rowA[KID_BAND], rowB[KID_BAND];
-    __shared__ double sF[KID_THREADS / 64];
+    __shared__ __attribute__((aligned(16))) double sA[F64RowK::SIZE];
+    __shared__ __attribute__((aligned(16))) double sB[F64RowK::SIZE];
+    __shared__ int rowA[F64_TILE], rowB[F64_TILE];
+    __shared__ double sF[F64_THREADS / 64];
 
     const int band = blockIdx.x % nb;
     const int p = (blockIdx.x / nb) & 3;                 // 0: GG, 1: RR, 2: GR, 3: RG
@@ -58,67 +47,38 @@ __global__ __launch_bounds__(KID_THREADS) void kid_band_kernel(const double* __r
     double* out_rows = out_s + (size_t)(p == 0 ? 0 : p == 1 ? 2 : p == 2 ? 4 : 5) * m;
     double* out_diag = out_s + (size_t)(p == 0 ? 1 : 3) * m;       // (written for p < 2 only)
 
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int lk = tid & 31, lr = tid >> 5;              // loader: feature within the chunk, first of its 8 rows
-    const int fr = lane & 15, fg = lane >> 4;            // MFMA fragment: row / column within the 16-block, k group
+    const int tid = threadIdx.x;
+    const int lk = F64RowK::own_k(tid, 0);               // loader: feature within the chunk
 
-    if (tid < KID_BAND) rowA[tid] = ia[min(band * KID_BAND + tid, m - 1)];
+    if (tid < F64_TILE) rowA[tid] = ia[min(band * F64_TILE + tid, m - 1)];
     __syncthreads();
-    long long offA[KID_LOADS], offB[KID_LOADS];
+    long long offA[F64_LOADS], offB[F64_LOADS];
 #pragma unroll
-    for (int i = 0; i < KID_LOADS; ++i) offA[i] = (long long)rowA[lr + 8 * i] * d;
+    for (int i = 0; i < F64_LOADS; ++i) offA[i] = (long long)rowA[F64RowK::own_index(tid, i)] * d;
 
     double rs[4] = {0.0, 0.0, 0.0, 0.0};
     double fsum = 0.0;
-    const int nchunks = (d + KID_KC - 1) / KID_KC;
+    const int nchunks = (d + F64_KC - 1) / F64_KC;
 
     for (int ct = 0; ct < nb; ++ct) {
         __syncthreads();
-        if (tid < KID_BAND) rowB[tid] = ib[min(ct * KID_BAND + tid, m - 1)];
+        if (tid < F64_TILE) rowB[tid] = ib[min(ct * F64_TILE + tid, m - 1)];
         __syncthreads();
 #pragma unroll
-        for (int i = 0; i < KID_LOADS; ++i) offB[i] = (long long)rowB[lr + 8 * i] * d;
+        for (int i = 0; i < F64_LOADS; ++i) offB[i] = (long long)rowB[F64RowK::own_index(tid, i)] * d;
 
         f64x4 acc[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[j] = f64x4{0.0, 0.0, 0.0, 0.0};
-        double pa[KID_LOADS], pb[KID_LOADS];
-        kid_fetch(A, offA, lk, d, pa);
-        kid_fetch(B, offB, lk, d, pb);
-        for (int c = 0; c < nchunks; ++c) {
-            __syncthreads();                             // the previous chunk's readers are done with sA / sB
-#pragma unroll
-            for (int i = 0; i < KID_LOADS; ++i) {
-                sA[(lr + 8 * i) * KID_LD + lk] = pa[i];
-                sB[(lr + 8 * i) * KID_LD + lk] = pb[i];
-            }
-            __syncthreads();
-            if (c + 1 < nchunks) {
-                kid_fetch(A, offA, (c + 1) * KID_KC + lk, d, pa);
-                kid_fetch(B, offB, (c + 1) * KID_KC + lk, d, pb);
-            }
-            const f64x2* qa = reinterpret_cast<const f64x2*>(&sA[(wave * 16 + fr) * KID_LD + fg * 8]);
-            f64x2 a2[4];
-#pragma unroll
-            for (int h = 0; h < 4; ++h) a2[h] = qa[h];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const f64x2* qb = reinterpret_cast<const f64x2*>(&sB[(j * 16 + fr) * KID_LD + fg * 8]);
-#pragma unroll
-                for (int h = 0; h < 4; ++h) {
-                    const f64x2 b2 = qb[h];
-                    acc[j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a2[h][0], b2[0], acc[j], 0, 0, 0);
-                    acc[j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a2[h][1], b2[1], acc[j], 0, 0, 0);
-                }
-            }
-        }
-        // epilogue of the tile: acc[j][r] is the dot product of band row wave*16 + fg + 4r and tile column j*16 + fr
+        f64_tile_mainloop<F64RowK, F64RowK, F64SlotBlocked>(
+            sA, sB, nchunks,
+            [&](long long c, double (&v)[F64_LOADS]) { kid_fetch(A, offA, (int)c * F64_KC + lk, d, v); },
+            [&](long long c, double (&v)[F64_LOADS]) { kid_fetch(B, offB, (int)c * F64_KC + lk, d, v); }, acc);
+        // epilogue of the tile, j outer and r inner: the order of the row sums and of the Frobenius share
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            const int col = ct * KID_BAND + j * 16 + fr;
+            const int col = ct * F64_TILE + f64_acc_col(tid, j);
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                const int row = band * KID_BAND + wave * 16 + fg + 4 * r;
+                const int row = band * F64_TILE + f64_acc_row(tid, r);
                 const double t = gamma * acc[j][r] + coef0;
                 double k = t;
                 for (int q = 1; q < degree; ++q) k *= t;
@@ -137,15 +97,13 @@ __global__ __launch_bounds__(KID_THREADS) void kid_band_kernel(const double* __r
     for (int r = 0; r < 4; ++r) {
         double v = rs[r];
 #pragma unroll
-        for (int o = 1; o < 16; o <<= 1) v += __shfl_xor(v, o, 64);
-        const int row = band * KID_BAND + wave * 16 + fg + 4 * r;
-        if (fr == 0 && row < m) out_rows[row] = v;
+        for (int o = 1; o < 16; o <<= 1) v += __shfl_xor(v, o, 64);      // a row's 16 columns sit in 16 consecutive lanes
+        const int row = band * F64_TILE + f64_acc_row(tid, r);
+        if (f64_acc_col(tid, 0) == 0 && row < m) out_rows[row] = v;
     }
     if (p < 3) {                                          // (uniform over the workgroup)
-        fsum = wave_sum_d(fsum);
-        if (lane == 0) sF[wave] = fsum;
-        __syncthreads();
-        if (tid == 0) frob[((size_t)s * 3 + p) * nb + band] = ((sF[0] + sF[1]) + sF[2]) + sF[3];
+        fsum = f64_workgroup_sum(fsum, sF);
+        if (tid == 0) frob[((size_t)s * 3 + p) * nb + band] = fsum;
     }
 }
 
@@ -160,7 +118,7 @@ __global__ __launch_bounds__(64) void kid_finish_kernel(const double* __restrict
     out[(size_t)s * (6 * (size_t)m + 3) + 6 * (size_t)m + p] = v;
 }
 
-inline int kid_bands(int m) { return (m + KID_BAND - 1) / KID_BAND; }
+inline int kid_bands(int m) { return (m + F64_TILE - 1) / F64_TILE; }
 
 }  // namespace gz
 
@@ -186,7 +144,7 @@ int gz_kid_sums(const double* codes_g, int n_g, const double* codes_r, int n_r, 
     const long long blocks = (long long)S * 4 * nb;
     if (blocks > 0x7fffffffll) return GZ_ERR_TOO_LARGE;
     double* frob = reinterpret_cast<double*>(workspace);
-    hipLaunchKernelGGL(kid_band_kernel, dim3((unsigned)blocks), dim3(KID_THREADS), 0, stream, codes_g, codes_r, d, idx, m,
+    hipLaunchKernelGGL(kid_band_kernel, dim3((unsigned)blocks), dim3(F64_THREADS), 0, stream, codes_g, codes_r, d, idx, m,
                        nb, gamma, coef0, degree, out, frob);
     const int rc = launch_status();
     if (rc != GZ_OK) return rc;

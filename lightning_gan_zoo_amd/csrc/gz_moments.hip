@@ -8,42 +8,29 @@
 //      row after row, into partial[block][column] (the workspace);
 //   2. moments_mean_kernel: mean[column] = (partial[0] + partial[1] + ...) / n, the blocks in block order;
 //   3. moments_tile_kernel: one workgroup per 64 x 64 tile (ti <= tj) of the upper triangle of cov, the whole sample axis
-//      inside it, so no partial covariance ever meets another one:
+//      inside it, so no partial covariance ever meets another one.  The tile runs on the fp64 tile core (gz_f64_tile.h:
+//      both operands [k][feature] images, the interleaved k-slot map):
 //      * the reduction index of the GEMM is the SAMPLE row.  A 64-feature slice of a row is 512 contiguous bytes, so a
-//        wave's global load is one row slice; a thread owns one feature (tid & 63) of each operand and subtracts that
-//        feature's mean as the value arrives.  Features >= d are zero in LDS; rows >= n are zero AFTER the subtraction
-//        (the centred value is masked, not the raw one);
-//      * the LDS image of an operand is [k][feature]: MOM_KC sample rows of MOM_LD doubles.  v_mfma_f64_16x16x4_f64 takes
-//        A as row = lane & 15, k = lane >> 4 and B as k = lane >> 4, col = lane & 15, so at MFMA step t a lane reads
-//        image[4 t + (lane >> 4)][16 block + (lane & 15)]: the 16 lanes of a k-slot read 16 consecutive doubles, 32
-//        consecutive banks.  ds_read_b64 banks are (byte / 4) % 64 and conflicts count inside a 32-lane half, i.e.
-//        between the k-slots 4t and 4t+1 (and 4t+2, 4t+3): MOM_LD = 64 + 16 doubles = 160 dwords = 32 (mod 64) puts the
-//        second slot on the other 32 banks, so the read is conflict-free.  The writes are a wave storing 64 consecutive
-//        doubles of one row;
-//      * wave w owns tile rows 16w .. 16w+15 and four 16 x 16 accumulators (the tile's 64 columns); C/D layout:
-//        col = lane & 15, row = (lane >> 4) + 4 * reg.  Chunks of MOM_KC rows travel global -> registers -> LDS one
-//        chunk ahead of the MFMAs; an entry is summed over the rows in row order (four at a time inside an MFMA);
+//        wave's global load is one row slice; a thread owns one feature of each operand and subtracts that feature's
+//        mean as the value arrives.  Features >= d are zero in LDS; rows >= n are zero AFTER the subtraction (the
+//        centred value is masked, not the raw one).  An entry is summed over the rows in row order (four at a time
+//        inside an MFMA);
 //      * epilogue: the tile times 1 / (n - 1) (the reciprocal is formed on the host, in fp64) goes through LDS (pitch 65:
 //        the transposed read walks 2 banks per lane) and is stored twice with rows of 64 lanes along the fast axis: as
 //        cov[ti rows][tj columns] and transposed as cov[tj rows][ti columns].  A diagonal tile stores only the entries
 //        on and above the diagonal and mirrors those, so cov[i][j] and cov[j][i] are one value's bits everywhere.
 // No floating-point atomics, a fixed order for every sum, nothing read from `mean`, `cov` or the workspace before this
 // call wrote it: two calls give equal bits.
-#include "gz_common.h"
+#include "gz_f64_tile.h"
 #include "../../include/gz_ops.h"
 
 namespace gz {
 
-typedef double f64x4 __attribute__((ext_vector_type(4)));
-
-constexpr int MOM_THREADS = 256;
-constexpr int MOM_TILE = 64;                  // features per tile side
-constexpr int MOM_KC = 32;                    // sample rows per LDS chunk
-constexpr int MOM_LD = MOM_TILE + 16;         // LDS row pitch in doubles (see above)
-constexpr int MOM_LOADS = MOM_KC * MOM_TILE / MOM_THREADS;      // doubles per thread, operand and chunk
+constexpr int MOM_THREADS = F64_THREADS;
+constexpr int MOM_TILE = F64_TILE;            // features per tile side
 constexpr int MOM_OUT_LD = MOM_TILE + 1;      // pitch of the epilogue's tile image
 constexpr int MOM_ROWS = 512;                 // rows per partial column sum
-static_assert(MOM_TILE * MOM_OUT_LD <= 2 * MOM_KC * MOM_LD, "the epilogue's tile image reuses the operand images");
+static_assert(MOM_TILE * MOM_OUT_LD <= 2 * F64KCol::SIZE, "the epilogue's tile image reuses the operand images");
 
 __global__ __launch_bounds__(MOM_THREADS) void moments_colsum_kernel(const double* __restrict__ act, long long n, int d,
                                                                      double* __restrict__ partial) {
@@ -66,12 +53,12 @@ __global__ __launch_bounds__(MOM_THREADS) void moments_mean_kernel(const double*
     mean[col] = s / (double)n;
 }
 
-// rows c0 + lr + 4 i of the chunk starting at row c0, feature f (mean m): centred, masked
-__device__ __forceinline__ void moments_fetch(const double* __restrict__ act, long long n, int d, long long c0, int lr,
-                                              int f, double m, double (&v)[MOM_LOADS]) {
+// the thread's 8 sample rows of the chunk starting at row c0, feature f (mean m): centred, masked
+__device__ __forceinline__ void moments_fetch(const double* __restrict__ act, long long n, int d, long long c0, int f,
+                                              double m, double (&v)[F64_LOADS]) {
 #pragma unroll
-    for (int i = 0; i < MOM_LOADS; ++i) {
-        const long long row = c0 + lr + 4 * i;
+    for (int i = 0; i < F64_LOADS; ++i) {
+        const long long row = c0 + F64KCol::own_k(threadIdx.x, i);
         v[i] = (row < n && f < d) ? act[row * d + f] - m : 0.0;
     }
 }
@@ -79,9 +66,7 @@ __device__ __forceinline__ void moments_fetch(const double* __restrict__ act, lo
 __global__ __launch_bounds__(MOM_THREADS) void moments_tile_kernel(const double* __restrict__ act, long long n, int d,
                                                                    int tiles, const double* __restrict__ mean,
                                                                    double inv, double* __restrict__ cov) {
-    __shared__ __attribute__((aligned(16))) double smem[2 * MOM_KC * MOM_LD];
-    double* sA = smem;
-    double* sB = smem + MOM_KC * MOM_LD;
+    __shared__ __attribute__((aligned(16))) double smem[2 * F64KCol::SIZE];
 
     int ti = 0, rest = (int)blockIdx.x;                  // tile (ti, tj), ti <= tj, rows of the triangle in order
     while (rest >= tiles - ti) {
@@ -90,48 +75,23 @@ __global__ __launch_bounds__(MOM_THREADS) void moments_tile_kernel(const double*
     }
     const int tj = ti + rest;
 
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int lf = tid & 63, lr = tid >> 6;              // loader: feature within the slice, first of its 8 rows
-    const int fr = lane & 15, fg = lane >> 4;            // MFMA fragment: row / column within the 16-block, k slot
+    const int tid = threadIdx.x;
+    const int lf = F64KCol::own_index(tid, 0);           // loader: feature within the slice
     const int fa = ti * MOM_TILE + lf, fb = tj * MOM_TILE + lf;
     const double ma = fa < d ? mean[fa] : 0.0, mb = fb < d ? mean[fb] : 0.0;
 
     f64x4 acc[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[j] = f64x4{0.0, 0.0, 0.0, 0.0};
-    double pa[MOM_LOADS], pb[MOM_LOADS];
-    moments_fetch(act, n, d, 0, lr, fa, ma, pa);
-    moments_fetch(act, n, d, 0, lr, fb, mb, pb);
-    const long long nchunks = (n + MOM_KC - 1) / MOM_KC;
-    for (long long c = 0; c < nchunks; ++c) {
-        __syncthreads();                                 // the previous chunk's readers are done with sA / sB
-#pragma unroll
-        for (int i = 0; i < MOM_LOADS; ++i) {
-            sA[(lr + 4 * i) * MOM_LD + lf] = pa[i];
-            sB[(lr + 4 * i) * MOM_LD + lf] = pb[i];
-        }
-        __syncthreads();
-        if (c + 1 < nchunks) {
-            moments_fetch(act, n, d, (c + 1) * MOM_KC, lr, fa, ma, pa);
-            moments_fetch(act, n, d, (c + 1) * MOM_KC, lr, fb, mb, pb);
-        }
-#pragma unroll
-        for (int t = 0; t < MOM_KC / 4; ++t) {
-            const double a = sA[(4 * t + fg) * MOM_LD + wave * 16 + fr];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const double b = sB[(4 * t + fg) * MOM_LD + j * 16 + fr];
-                acc[j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, acc[j], 0, 0, 0);
-            }
-        }
-    }
+    f64_tile_mainloop<F64KCol, F64KCol, F64SlotInterleaved>(
+        smem, smem + F64KCol::SIZE, (n + F64_KC - 1) / F64_KC,
+        [&](long long c, double (&v)[F64_LOADS]) { moments_fetch(act, n, d, c * F64_KC, fa, ma, v); },
+        [&](long long c, double (&v)[F64_LOADS]) { moments_fetch(act, n, d, c * F64_KC, fb, mb, v); }, acc);
 
-    // acc[j][r] is the centred dot product of features ti*64 + wave*16 + fg + 4r and tj*64 + j*16 + fr
-    __syncthreads();                                     // the last chunk's readers are done with sA / sB
+    // acc[j][r] is the centred dot product of features ti*64 + f64_acc_row(r) and tj*64 + f64_acc_col(j)
+    __syncthreads();                                     // the last chunk's readers are done with the images
 #pragma unroll
     for (int j = 0; j < 4; ++j)
 #pragma unroll
-        for (int r = 0; r < 4; ++r) smem[(wave * 16 + fg + 4 * r) * MOM_OUT_LD + j * 16 + fr] = acc[j][r] * inv;
+        for (int r = 0; r < 4; ++r) smem[f64_acc_row(tid, r) * MOM_OUT_LD + f64_acc_col(tid, j)] = acc[j][r] * inv;
     __syncthreads();
     const int hi = tid & 63;
     for (int lo = tid >> 6; lo < MOM_TILE; lo += MOM_THREADS / 64) {

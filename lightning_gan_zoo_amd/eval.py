@@ -219,6 +219,33 @@ def _sq(a):
     return a.dot(a)
 
 
+def _mmd2(m, sx, sy, sxy):
+    """The unbiased MMD^2 estimate from the sums of K_xx and K_yy without their diagonals and the sum of K_xy; scalars
+    (one subset) or [S] arrays."""
+    return (sx + sy) / (m * (m - 1)) - 2 * sxy / (m * m)
+
+
+def _mmd2_variance(m, var_at_m, sx, sy, sxy, sx2, sy2, sxy2, dxx, dyy, rx2, ry2, cxy1_2, cxy0_2):
+    """The estimator's variance estimate (callback_inception_metrics.py:57-133) from reduced quantities, scalars or [S]
+    arrays: ``s*`` the sums of ``_mmd2``, ``s*2`` the sums of squared entries (diagonals excluded for xx, yy),
+    ``dxx = <rx, cxy1>``, ``dyy = <ry, cxy0>`` and the squared norms of the row sums rx, ry (without diagonal) and of
+    K_xy's row sums cxy1 and column sums cxy0.  The callers make the reductions; the expressions exist once."""
+    m1, m2 = m - 1, m - 2
+    zeta1 = (1 / (m * m1 * m2) * (rx2 - sx2 + ry2 - sy2)
+             - 1 / (m * m1) ** 2 * (sx ** 2 + sy ** 2)
+             + 1 / (m * m * m1) * (cxy1_2 + cxy0_2 - 2 * sxy2)
+             - 2 / m ** 4 * sxy ** 2
+             - 2 / (m * m * m1) * (dxx + dyy)
+             + 2 / (m ** 3 * m1) * (sx + sy) * sxy)
+    zeta2 = (1 / (m * m1) * (sx2 + sy2)
+             - 1 / (m * m1) ** 2 * (sx ** 2 + sy ** 2)
+             + 2 / (m * m) * sxy2
+             - 2 / m ** 4 * sxy ** 2
+             - 4 / (m * m * m1) * (dxx + dyy)
+             + 4 / (m ** 3 * m1) * (sx + sy) * sxy)
+    return 4 * (var_at_m - 2) / (var_at_m * (var_at_m - 1)) * zeta1 + 2 / (var_at_m * (var_at_m - 1)) * zeta2
+
+
 def _mmd2_and_variance(k_xx, k_xy, k_yy, var_at_m=None, ret_var=True):
     """Unbiased MMD^2 estimate and its variance estimate from three m x m kernel matrices
     (callback_inception_metrics.py:57-133, the 'unbiased' estimator with explicit diagonals)."""
@@ -230,7 +257,7 @@ def _mmd2_and_variance(k_xx, k_xy, k_yy, var_at_m=None, ret_var=True):
     ry = k_yy.sum(axis=1) - dy
     cxy0, cxy1 = k_xy.sum(axis=0), k_xy.sum(axis=1)
     sx, sy, sxy = rx.sum(), ry.sum(), cxy0.sum()
-    mmd2 = (sx + sy) / (m * (m - 1)) - 2 * sxy / (m * m)
+    mmd2 = _mmd2(m, sx, sy, sxy)
     if not ret_var:
         return mmd2
     sx2 = _sq(k_xx) - _sq(dx)
@@ -238,21 +265,8 @@ def _mmd2_and_variance(k_xx, k_xy, k_yy, var_at_m=None, ret_var=True):
     sxy2 = _sq(k_xy)
     dxx = rx.dot(cxy1)
     dyy = ry.dot(cxy0)
-    m1, m2 = m - 1, m - 2
-    zeta1 = (1 / (m * m1 * m2) * (_sq(rx) - sx2 + _sq(ry) - sy2)
-             - 1 / (m * m1) ** 2 * (sx ** 2 + sy ** 2)
-             + 1 / (m * m * m1) * (_sq(cxy1) + _sq(cxy0) - 2 * sxy2)
-             - 2 / m ** 4 * sxy ** 2
-             - 2 / (m * m * m1) * (dxx + dyy)
-             + 2 / (m ** 3 * m1) * (sx + sy) * sxy)
-    zeta2 = (1 / (m * m1) * (sx2 + sy2)
-             - 1 / (m * m1) ** 2 * (sx ** 2 + sy ** 2)
-             + 2 / (m * m) * sxy2
-             - 2 / m ** 4 * sxy ** 2
-             - 4 / (m * m * m1) * (dxx + dyy)
-             + 4 / (m ** 3 * m1) * (sx + sy) * sxy)
-    var = 4 * (var_at_m - 2) / (var_at_m * (var_at_m - 1)) * zeta1 + 2 / (var_at_m * (var_at_m - 1)) * zeta2
-    return mmd2, var
+    return mmd2, _mmd2_variance(m, var_at_m, sx, sy, sxy, sx2, sy2, sxy2, dxx, dyy, _sq(rx), _sq(ry), _sq(cxy1),
+                                _sq(cxy0))
 
 
 def polynomial_mmd(codes_g, codes_r, degree=3, gamma=None, coef0=1, var_at_m=None, ret_var=True):
@@ -295,7 +309,7 @@ def _mmd2_and_variance_from_sums(sums, m, var_at_m=None, ret_var=True):
     ry = sums[:, 2 * m:3 * m] - dy
     cxy1, cxy0 = sums[:, 4 * m:5 * m], sums[:, 5 * m:6 * m]
     sx, sy, sxy = rx.sum(axis=1), ry.sum(axis=1), cxy0.sum(axis=1)
-    mmd2 = (sx + sy) / (m * (m - 1)) - 2 * sxy / (m * m)
+    mmd2 = _mmd2(m, sx, sy, sxy)
     if not ret_var:
         return mmd2
 
@@ -307,21 +321,8 @@ def _mmd2_and_variance_from_sums(sums, m, var_at_m=None, ret_var=True):
     sxy2 = sums[:, 6 * m + 2]
     dxx = np.einsum("sm,sm->s", rx, cxy1)
     dyy = np.einsum("sm,sm->s", ry, cxy0)
-    m1, m2 = m - 1, m - 2
-    zeta1 = (1 / (m * m1 * m2) * (sq(rx) - sx2 + sq(ry) - sy2)
-             - 1 / (m * m1) ** 2 * (sx ** 2 + sy ** 2)
-             + 1 / (m * m * m1) * (sq(cxy1) + sq(cxy0) - 2 * sxy2)
-             - 2 / m ** 4 * sxy ** 2
-             - 2 / (m * m * m1) * (dxx + dyy)
-             + 2 / (m ** 3 * m1) * (sx + sy) * sxy)
-    zeta2 = (1 / (m * m1) * (sx2 + sy2)
-             - 1 / (m * m1) ** 2 * (sx ** 2 + sy ** 2)
-             + 2 / (m * m) * sxy2
-             - 2 / m ** 4 * sxy ** 2
-             - 4 / (m * m * m1) * (dxx + dyy)
-             + 4 / (m ** 3 * m1) * (sx + sy) * sxy)
-    var = 4 * (var_at_m - 2) / (var_at_m * (var_at_m - 1)) * zeta1 + 2 / (var_at_m * (var_at_m - 1)) * zeta2
-    return mmd2, var
+    return mmd2, _mmd2_variance(m, var_at_m, sx, sy, sxy, sx2, sy2, sxy2, dxx, dyy, sq(rx), sq(ry), sq(cxy1),
+                                sq(cxy0))
 
 
 def draw_kid_subsets(n_g, n_r, n_subsets, subset_size):

@@ -1,14 +1,35 @@
-"""Shared by tests/test_kid_cpu.py and tests/test_kid_gpu.py: the fixture construction, numpy's version of the kernel's
-output and the forward error bounds of the sums."""
+"""Shared by tests/test_kid_cpu.py, tests/test_kid_gpu.py and tests/test_f64_tile_parent_bits_gpu.py: the fixture
+construction, numpy's version of the kernel's output and the forward error bounds of the sums."""
 import numpy as np
 
 U = 2.0 ** -53
+N_G, N_R = 400, 360
+_codes = {}
 
 
 def activations(seed, n, d, shift):          # same construction as tests/golden/make_eval_golden.py
     rng = np.random.RandomState(seed)
     basis = rng.randn(d, d) / np.sqrt(d)
     return rng.randn(n, d).dot(basis) + shift * rng.rand(d)
+
+
+def mixed_sign_codes(d):
+    if d not in _codes:
+        rng = np.random.RandomState(1000 + d)
+        _codes[d] = (rng.randn(N_G, d) * 1.5 + 0.2, rng.randn(N_R, d) - 0.1)
+    return _codes[d]
+
+
+def subset_rows(m, S, seed):
+    """[S, 2, m] rows without repetition inside a subset; every subset holds rows 0 and n-1 of both sets (so row 0 is
+    shared by any two subsets)."""
+    rng = np.random.RandomState(seed)
+    idx = np.empty((S, 2, m), dtype=np.int32)
+    for s in range(S):
+        for slot, n in ((0, N_G), (1, N_R)):
+            rows = np.concatenate([[0, n - 1], 1 + rng.permutation(n - 2)])[:m]
+            idx[s, slot] = rng.permutation(rows)
+    return idx
 
 
 def host_rows(n_g, n_r, n_subsets, subset_size):

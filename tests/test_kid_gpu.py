@@ -10,33 +10,12 @@ import pytest
 import torch
 
 from helpers import GOLDEN_DIR
-from kid_support import U, activations, numpy_sums, sums_bounds
+from kid_support import N_G, N_R, U, activations, mixed_sign_codes, numpy_sums, subset_rows, sums_bounds
 
 pytestmark = pytest.mark.gpu
 
-N_G, N_R = 400, 360
 SHAPES = [(3, 1, 1), (16, 4, 2), (17, 7, 3), (65, 48, 2), (150, 48, 7), (130, 2048, 2)]          # (m, d, S)
 KERNELS = [(3, None, 1.0), (1, 0.05, 0.0), (2, 0.05, 1.0), (3, None, 0.0)]                      # (degree, gamma, coef0)
-_codes = {}
-
-
-def mixed_sign_codes(d):
-    if d not in _codes:
-        rng = np.random.RandomState(1000 + d)
-        _codes[d] = (rng.randn(N_G, d) * 1.5 + 0.2, rng.randn(N_R, d) - 0.1)
-    return _codes[d]
-
-
-def subset_rows(m, S, seed):
-    """[S, 2, m] rows without repetition inside a subset; every subset holds rows 0 and n-1 of both sets (so row 0 is
-    shared by any two subsets)."""
-    rng = np.random.RandomState(seed)
-    idx = np.empty((S, 2, m), dtype=np.int32)
-    for s in range(S):
-        for slot, n in ((0, N_G), (1, N_R)):
-            rows = np.concatenate([[0, n - 1], 1 + rng.permutation(n - 2)])[:m]
-            idx[s, slot] = rng.permutation(rows)
-    return idx
 
 
 def _dev(a):
