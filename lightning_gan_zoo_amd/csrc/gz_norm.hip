@@ -8,6 +8,18 @@
 // every pass is "row sums by wavefront shuffle" (+ a tiny finalize over rows) or a float4
 // elementwise apply, so each tensor is streamed once per pass with 16-byte accesses.
 // `per_channel` = 1 selects coefficient index row % C (BatchNorm), 0 selects the row itself.
+//
+// The file is a handful of pieces, each written once, and kernels that combine them (DESIGN 3.3 has the table):
+//   row_walk, lane_q4s    wavefront -> rows with the grid-stride loop; one lane's float4s of a row
+//   Coef                  (scale, shift, mean, rstd) with loader and store; bwd_terms / bwd_dx / row_bwd_k per element
+//   column_sums           one wavefront sums an f32x2 column in fp64 (the per-channel finalize kernels)
+//   bn_finalize, bn_bwd_k sums -> coefficients (+ running buffers); sums -> k1, k2 and the affine gradients
+//   bn_slice(_walk)       the workgroup decode and slice walk of the two fused BatchNorm kernels
+//   ew4_range             the float4 grid-stride loop of the elementwise kernels
+// Every piece fixes an ORDER of floating-point operations; tests/test_norm_parent_bits_gpu.py holds all of them to
+// recorded bits.
+#include <type_traits>
+
 #include "gz_common.h"
 #include "gz_knobs.h"
 #include "../../include/gz_ops.h"
@@ -16,6 +28,9 @@ namespace gz {
 
 constexpr int PW_THREADS = 256;
 
+// ---------------------------------------------------------------------------
+// row walk
+// ---------------------------------------------------------------------------
 struct RowGeom {
     int rows, q4;       // rows, float4 per row
     int lpr, rpw;       // lanes per row (pow2 <= 64), rows per wave
@@ -48,44 +63,235 @@ __device__ __forceinline__ void sub_reduce(float (&s)[NS], int lpr) {
     }
 }
 
+// The loop skeletons of this file are ranges, `for (i : strided(...))`, not helpers that take the body as a callable:
+// a function boundary around a loop body, even an always-inline one, changes where the compiler contracts products and
+// sums, and with it the output bits (tests/test_norm_parent_bits_gpu.py).
+template <class T>
+struct Strided {        // first, first + step, ... < last
+    T first, last, step;
+    struct It {
+        T i, step;
+        __device__ __forceinline__ T operator*() const { return i; }
+        __device__ __forceinline__ It& operator++() { i += step; return *this; }
+        __device__ __forceinline__ bool operator!=(const It& end) const { return i < end.i; }
+    };
+    __device__ __forceinline__ It begin() const { return It{first, step}; }
+    __device__ __forceinline__ It end() const { return It{last, T(0)}; }
+};
+
+// Row walk: a wavefront takes rpw rows at a time, lpr lanes ("sub-wave") per row, grid-stride over the rows: this
+// lane's rows are row0 + sub for row0 in row0s, and l is its place in the sub-wave.  A sub-wave past the last row still
+// comes along (row >= g.rows: not live), because sub_reduce shuffles across the whole wavefront.
+struct RowWalk {
+    int sub, l;
+    Strided<long long> row0s;
+};
+
+__device__ __forceinline__ RowWalk row_walk(const RowGeom& g) {
+    const int lane = threadIdx.x & 63;
+    const int wave = (blockIdx.x * PW_THREADS + threadIdx.x) >> 6;
+    const int nwaves = (gridDim.x * PW_THREADS) >> 6;
+    const int sub = lane / g.lpr, l = lane % g.lpr;
+    return RowWalk{sub, l, {(long long)wave * g.rpw, (long long)g.rows, (long long)nwaves * g.rpw}};
+}
+
+__device__ __forceinline__ const f32x4* row_ptr(const float* base, long long row, const RowGeom& g) {
+    return reinterpret_cast<const f32x4*>(base) + row * g.q4;
+}
+
+// The lane's float4s of a live row, q = l, l + lpr, ... < q4 (none of a dead row): the streaming pass of the row
+// kernels.  (rownorm_act_fused_kernel and rownorm_bwd_fused_kernel also have a register-cached form of their passes,
+// written out next to the streaming one: see there.)
+__device__ __forceinline__ Strided<int> lane_q4s(const RowGeom& g, bool live, int l) {
+    return Strided<int>{l, live ? g.q4 : 0, g.lpr};
+}
+
+// ---------------------------------------------------------------------------
+// coefficients and element terms
+// ---------------------------------------------------------------------------
+// coef[0*n..] = scale, coef[1*n..] = shift, coef[2*n..] = mean, coef[3*n..] = rstd   (n = number of coefficient entries)
+struct Coef {
+    float sc, sh, mean, rstd;
+};
+
+__device__ __forceinline__ Coef load_coef(const float* __restrict__ coef, int ncoef, int ci) {
+    return Coef{coef[ci], coef[ncoef + ci], coef[2 * ncoef + ci], coef[3 * ncoef + ci]};
+}
+
+__device__ __forceinline__ void store_coef(float* __restrict__ coef, int ncoef, int ci, const Coef& k) {
+    coef[ci] = k.sc;
+    coef[ncoef + ci] = k.sh;
+    coef[2 * ncoef + ci] = k.mean;
+    coef[3 * ncoef + ci] = k.rstd;
+}
+
+// gamma / beta (and their gradients) of row r: per channel (0), per row (1), or per row in a packed [N][2C] array (2)
+__device__ __forceinline__ int affine_index(int r, int C, int affine_per_row) {
+    return affine_per_row == 2 ? (r / C) * 2 * C + r % C : (affine_per_row ? r : r % C);
+}
+
+// coefficient entry of a row: the row itself, or (per_channel) its channel within its statistics group.  (The apply
+// kernels index by float4 and keep their FastDiv form, coef_index below: a `%` there costs the hot path instructions.)
+__device__ __forceinline__ int row_coef_index(long long row, int C, int per_channel, int group_rows) {
+    return per_channel ? (int)(row % C) + (group_rows ? (int)(row / group_rows) * C : 0) : (int)row;
+}
+
+__device__ __forceinline__ float act_grad_z(float z, int act, float slope) {
+    if (act == ACT_RELU) return z > 0.f ? 1.f : 0.f;
+    if (act == ACT_LRELU) return z > 0.f ? 1.f : slope;
+    return 1.f;
+}
+
+// first backward, per element:
+//   z = x*scale + shift, m = act'(z), dz = gout * m, xh = (x - mean) * rstd
+//   dx = scale * (dz - k1 - xh*k2),  k1 = mean(dz), k2 = mean(dz*xh) over the statistics group
+struct BwdTerms {
+    float dz, xh;
+};
+
+__device__ __forceinline__ float bwd_mask(float x, const Coef& k, int act, float slope) {
+    return act_grad_z(x * k.sc + k.sh, act, slope);
+}
+
+__device__ __forceinline__ BwdTerms bwd_terms(float x, float g, const Coef& k, int act, float slope) {
+    return BwdTerms{g * bwd_mask(x, k, act, slope), (x - k.mean) * k.rstd};
+}
+
+__device__ __forceinline__ float bwd_dx(float sc, float dz, float xh, float k1, float k2) {
+    return sc * (dz - k1 - xh * k2);
+}
+
+__device__ __forceinline__ f32x4 norm_act4(const f32x4& v, float sc, float sh, int act, float slope) {
+    f32x4 o;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) o[e] = act_fwd(v[e] * sc + sh, act, slope);
+    return o;
+}
+
+// ---------------------------------------------------------------------------
+// float4 grid-stride loop of the elementwise kernels
+// ---------------------------------------------------------------------------
+__device__ __forceinline__ Strided<long long> ew4_range(long long total4) {
+    return Strided<long long>{(long long)blockIdx.x * PW_THREADS + threadIdx.x, total4, (long long)gridDim.x * PW_THREADS};
+}
+
+__device__ __forceinline__ f32x4 ld4(const float* p, long long i) { return reinterpret_cast<const f32x4*>(p)[i]; }
+__device__ __forceinline__ void st4(float* p, long long i, const f32x4& v) { reinterpret_cast<f32x4*>(p)[i] = v; }
+
+// ---------------------------------------------------------------------------
+// per-channel finalize pieces
+// ---------------------------------------------------------------------------
+// One wavefront per channel: sums (x, y) of the `count` entries sums[(first + n) * C + c] in fp64, `lanes` threads
+// striding over n, shuffle-combined within each wavefront.
+__device__ __forceinline__ void column_sums(const f32x2* __restrict__ sums, int first, int count, int C, int c, int lane,
+                                            int lanes, double& s1, double& s2) {
+    s1 = 0.0;
+    s2 = 0.0;
+    for (int n = lane; n < count; n += lanes) {
+        const f32x2 v = sums[(long long)(first + n) * C + c];
+        s1 += (double)v.x;
+        s2 += (double)v.y;
+    }
+    s1 = wave_sum_d(s1);
+    s2 = wave_sum_d(s2);
+}
+
+// BatchNorm forward finalize: (sum x, sum x^2) over `cnt` elements of channel c -> coefficients; write = true stores
+// them as entry ci and updates the running buffers (unbiased variance), when there are any.
+struct BnOut {
+    float* coef;
+    int ncoef;
+    float *running_mean, *running_var;
+    float momentum;
+};
+
+__device__ __forceinline__ Coef bn_finalize(double s1, double s2, double cnt, const float* __restrict__ gamma,
+                                            const float* __restrict__ beta, float eps, int c, int ci, bool write,
+                                            const BnOut& o) {
+    const double mean = s1 / cnt;
+    double var = s2 / cnt - mean * mean;
+    if (var < 0.0) var = 0.0;
+    Coef k;
+    k.rstd = (float)(1.0 / sqrt(var + (double)eps));
+    const float ga = gamma ? gamma[c] : 1.f, be = beta ? beta[c] : 0.f;
+    k.sc = ga * k.rstd;
+    k.sh = be - (float)mean * k.sc;
+    k.mean = (float)mean;
+    if (write) {
+        store_coef(o.coef, o.ncoef, ci, k);
+        if (o.running_mean) {
+            const double unbiased = cnt > 1.0 ? var * cnt / (cnt - 1.0) : var;
+            o.running_mean[c] = (1.f - o.momentum) * o.running_mean[c] + o.momentum * (float)mean;
+            o.running_var[c] = (1.f - o.momentum) * o.running_var[c] + o.momentum * (float)unbiased;
+        }
+    }
+    return k;
+}
+
+// count > 0: the sums are per-tile partials of a convolution over `count` elements per group, not rows of `inner`
+__device__ __forceinline__ double bn_count(double count, int Ng, int inner) {
+    return count > 0.0 ? count : (double)Ng * inner;
+}
+
+// BatchNorm backward finalize of one (group, channel): k1 = mean(dz), k2 = mean(dz*xh), stored as entry ci of k[2][nk]
+// when k is there; the sums join t, which becomes the affine gradients of the channel once every group is in.
+struct AffineSums {
+    double t1 = 0.0, t2 = 0.0;
+};
+
+__device__ __forceinline__ f32x2 bn_bwd_k(double s1, double s2, double cnt, float* __restrict__ k, int nk, int ci,
+                                          bool write, AffineSums& t) {
+    const f32x2 r = {(float)(s1 / cnt), (float)(s2 / cnt)};
+    if (write && k) {
+        k[ci] = r.x;
+        k[nk + ci] = r.y;
+    }
+    t.t1 += s1;
+    t.t2 += s2;
+    return r;
+}
+
+// accumulate != 0: dgamma / dbeta already hold earlier contributions -- the gradient sink of functional/_base.py --
+// and are added to
+__device__ __forceinline__ void affine_grad_store(float* __restrict__ dgamma, float* __restrict__ dbeta, int c,
+                                                  const AffineSums& t, int accumulate) {
+    if (dgamma) dgamma[c] = (accumulate ? dgamma[c] : 0.f) + (float)t.t2;
+    if (dbeta) dbeta[c] = (accumulate ? dbeta[c] : 0.f) + (float)t.t1;
+}
+
 // ---------------------------------------------------------------------------
 // forward statistics
 // ---------------------------------------------------------------------------
 // sums[row] = (sum x, sum x^2)
 __global__ __launch_bounds__(PW_THREADS) void row_sums_kernel(const float* __restrict__ x, f32x2* __restrict__ sums,
                                                               RowGeom g) {
-    const int lane = threadIdx.x & 63;
-    const int wave = (blockIdx.x * PW_THREADS + threadIdx.x) >> 6;
-    const int nwaves = (gridDim.x * PW_THREADS) >> 6;
-    const int sub = lane / g.lpr, l = lane % g.lpr;
-    for (long long row0 = (long long)wave * g.rpw; row0 < g.rows; row0 += (long long)nwaves * g.rpw) {
-        long long row = row0 + sub;
+    const RowWalk w = row_walk(g);
+    for (const long long row0 : w.row0s) {
+        const long long row = row0 + w.sub;
+        const bool live = row < g.rows;
+        const int l = w.l;
         float s[2] = {0.f, 0.f};
-        if (row < g.rows) {
-            const f32x4* p = reinterpret_cast<const f32x4*>(x) + row * g.q4;
-            for (int q = l; q < g.q4; q += g.lpr) {
-                f32x4 v = p[q];
-                s[0] += (v.x + v.y) + (v.z + v.w);
-                s[1] += (v.x * v.x + v.y * v.y) + (v.z * v.z + v.w * v.w);
-            }
+        const f32x4* p = row_ptr(x, row, g);
+        for (const int q : lane_q4s(g, live, l)) {
+            const f32x4 v = p[q];
+            s[0] += (v.x + v.y) + (v.z + v.w);
+            s[1] += (v.x * v.x + v.y * v.y) + (v.z * v.z + v.w * v.w);
         }
         sub_reduce<2>(s, g.lpr);
-        if (row < g.rows && l == 0) sums[row] = f32x2{s[0], s[1]};
+        if (live && l == 0) sums[row] = f32x2{s[0], s[1]};
     }
 }
 
 // out[c] = sum_n sums[n*C + c].x : second half of gz_channel_sum (bias gradient of a convolution)
 __global__ __launch_bounds__(64) void channel_sum_finalize_kernel(const f32x2* __restrict__ sums, float* __restrict__ out,
                                                                   int N, int C) {
-    const int c = blockIdx.x, lane = threadIdx.x;
-    double s = 0.0;
-    for (int n = lane; n < N; n += 64) s += (double)sums[(long long)n * C + c].x;
-    s = wave_sum_d(s);
-    if (lane == 0) out[c] = (float)s;
+    double s, unused;
+    column_sums(sums, 0, N, C, blockIdx.x, threadIdx.x, 64, s, unused);
+    if (threadIdx.x == 0) out[blockIdx.x] = (float)s;
 }
 
-// BatchNorm finalize: one wavefront per channel; lanes stride over n, fp64 shuffle-combine.
-// coef[0*C..] = scale, coef[1*C..] = shift, coef[2*C..] = mean, coef[3*C..] = rstd
+// BatchNorm finalize: one wavefront per channel (WAVES = 8: eight share the walk over many partial rows -- the
+// per-tile statistics of a large layer -- and meet in LDS).
 // groups > 1 (round 4): the batch is `groups` independent statistics groups stacked along n -- the discriminator
 // applied to [real; fake] in ONE pass behaves like the reference's two calls: group g owns rows [g N/groups,
 // (g+1) N/groups), gets its own coefficients (index g*C + c, `count` elements per group) and updates the running
@@ -99,17 +305,12 @@ __global__ __launch_bounds__(64 * WAVES) void bn_finalize_kernel(const f32x2* __
                                                          double count, int groups) {
     const int c = blockIdx.x, lane = threadIdx.x;
     if (c == 0 && lane == 0 && nbt) *nbt += groups;
-    const int Ng = N / groups, NC = groups * C;
+    const int Ng = N / groups;
+    const BnOut o = {coef, groups * C, running_mean, running_var, momentum};
     for (int g = 0; g < groups; ++g) {
-        double s1 = 0.0, s2 = 0.0;
-        for (int n = lane; n < Ng; n += 64 * WAVES) {
-            f32x2 v = sums[(long long)(g * Ng + n) * C + c];
-            s1 += (double)v.x;
-            s2 += (double)v.y;
-        }
-        s1 = wave_sum_d(s1);
-        s2 = wave_sum_d(s2);
-        if constexpr (WAVES > 1) {       // many partial rows (per-tile statistics of a large layer): 4 wavefronts share the walk
+        double s1, s2;
+        column_sums(sums, g * Ng, Ng, C, c, lane, 64 * WAVES, s1, s2);
+        if constexpr (WAVES > 1) {
             __shared__ double part[WAVES][2];
             __syncthreads();             // (the previous group's readers are done)
             if ((lane & 63) == 0) {
@@ -124,24 +325,7 @@ __global__ __launch_bounds__(64 * WAVES) void bn_finalize_kernel(const f32x2* __
                 s2 += part[w][1];
             }
         }
-        if (lane != 0) continue;
-        double cnt = count > 0.0 ? count : (double)Ng * inner;      // count > 0: `sums` are per-tile partials, not rows
-        double mean = s1 / cnt;
-        double var = s2 / cnt - mean * mean;
-        if (var < 0.0) var = 0.0;
-        float rstd = (float)(1.0 / sqrt(var + (double)eps));
-        float ga = gamma ? gamma[c] : 1.f, be = beta ? beta[c] : 0.f;
-        float scale = ga * rstd;
-        const int ci = g * C + c;
-        coef[ci] = scale;
-        coef[NC + ci] = be - (float)mean * scale;
-        coef[2 * NC + ci] = (float)mean;
-        coef[3 * NC + ci] = rstd;
-        if (running_mean) {
-            double unbiased = cnt > 1.0 ? var * cnt / (cnt - 1.0) : var;
-            running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * (float)mean;
-            running_var[c] = (1.f - momentum) * running_var[c] + momentum * (float)unbiased;
-        }
+        if (lane == 0) bn_finalize(s1, s2, bn_count(count, Ng, inner), gamma, beta, eps, c, g * C + c, true, o);
     }
 }
 
@@ -153,10 +337,7 @@ __global__ void bn_eval_coef_kernel(const float* __restrict__ gamma, const float
     if (c >= C) return;
     float rstd = 1.f / sqrtf(rv[c] + eps);
     float ga = gamma ? gamma[c] : 1.f, be = beta ? beta[c] : 0.f;
-    coef[c] = ga * rstd;
-    coef[C + c] = be - rm[c] * ga * rstd;
-    coef[2 * C + c] = rm[c];
-    coef[3 * C + c] = rstd;
+    store_coef(coef, C, c, Coef{ga * rstd, be - rm[c] * ga * rstd, rm[c], rstd});
 }
 
 // ---------------------------------------------------------------------------
@@ -171,6 +352,7 @@ struct ApplyGeom {
     FastDiv div_grows;
 };
 
+// row_coef_index for float4 number i4 of the tensor, by FastDiv
 __device__ __forceinline__ int coef_index(long long i4, const ApplyGeom& g) {
     uint32_t row = fdiv((uint32_t)i4, g.div_q4);
     if (g.per_channel) {
@@ -184,15 +366,10 @@ __global__ __launch_bounds__(PW_THREADS) void norm_act_apply_kernel(const float*
                                                                     const float* __restrict__ coef,
                                                                     float* __restrict__ out, ApplyGeom g, int act,
                                                                     float slope) {
-    const long long stride = (long long)gridDim.x * PW_THREADS;
-    for (long long i = (long long)blockIdx.x * PW_THREADS + threadIdx.x; i < g.total4; i += stride) {
-        int ci = coef_index(i, g);
-        float sc = coef[ci], sh = coef[g.ncoef + ci];
-        f32x4 v = reinterpret_cast<const f32x4*>(x)[i];
-        f32x4 o;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) o[k] = act_fwd(v[k] * sc + sh, act, slope);
-        reinterpret_cast<f32x4*>(out)[i] = o;
+    for (const long long i : ew4_range(g.total4)) {
+        const int ci = coef_index(i, g);
+        const float sc = coef[ci], sh = coef[g.ncoef + ci];
+        st4(out, i, norm_act4(ld4(x, i), sc, sh, act, slope));
     }
 }
 
@@ -234,6 +411,44 @@ static BnFuse bn_fuse_geom(int N, int C, int inner, int groups) {
     return f;
 }
 
+static int bn_fuse_grid(const BnFuse& f) { return (f.C / f.CB) * f.groups * f.S; }
+
+// what blockIdx.x is in a BnFuse launch: slice s of statistics group g, channels c0 .. c0 + CB
+struct BnSlice {
+    int s, g, c0;
+    bool owner;
+};
+
+__device__ __forceinline__ BnSlice bn_slice(const BnFuse& f) {
+    const int s = blockIdx.x % f.S, bg = blockIdx.x / f.S, g = bg % f.groups, c0 = (bg / f.groups) * f.CB;
+    return BnSlice{s, g, c0, g == 0 && s == 0};
+}
+
+// the float4s of the slice: i in is, slice_at(f, w, i) = (number in the tensor, channel within the block).  (The last
+// slice of a group is empty when S does not divide Ng evenly enough.)
+struct BnSliceWalk {
+    int n0, c0;
+    Strided<int> is;
+};
+
+__device__ __forceinline__ BnSliceWalk bn_slice_walk(const BnFuse& f, const BnSlice& w) {
+    const int n0 = w.g * f.Ng + w.s * f.P;
+    const int n1 = min(w.g * f.Ng + f.Ng, n0 + f.P);
+    return BnSliceWalk{n0, w.c0, {(int)threadIdx.x, (n1 - n0) * f.run4, PW_THREADS}};
+}
+
+struct SliceAt {
+    long long idx;
+    uint32_t cb;
+};
+
+__device__ __forceinline__ SliceAt slice_at(const BnFuse& f, const BnSliceWalk& w, int i) {
+    const uint32_t p = fdiv((uint32_t)i, f.div_run);
+    const uint32_t rem = (uint32_t)i - p * (uint32_t)f.run4;
+    const uint32_t cb = fdiv(rem, f.div_q4);
+    return SliceAt{((long long)(w.n0 + (int)p) * f.C + w.c0) * f.q4 + rem, cb};
+}
+
 // sums of (x, y) pairs over `count` entries strided by `stride` f32x2, for the CB channels of this workgroup: thread t
 // takes channel t % CB and entries t / CB, t / CB + 256 / CB, ...; the partial sums meet in LDS by halving.  Result for
 // channel cb in red[cb] (valid for all threads after the call).
@@ -266,64 +481,37 @@ __global__ __launch_bounds__(PW_THREADS) void bn_apply_fused_kernel(
     __shared__ double red[PW_THREADS][2];
     __shared__ float mine[16][2];
     const int tid = threadIdx.x;
-    const int s = blockIdx.x % f.S, bg = blockIdx.x / f.S, g = bg % f.groups, c0 = (bg / f.groups) * f.CB;
-    const bool owner = g == 0 && s == 0;
-    const int Rg = rows / f.groups, NC = f.groups * f.C;
+    const BnSlice w = bn_slice(f);
+    const int Rg = rows / f.groups;
+    const BnOut o = {coef, f.groups * f.C, running_mean, running_var, momentum};
     for (int gg = 0; gg < f.groups; ++gg) {
-        if (!owner && gg != g) continue;                       // (uniform per workgroup)
-        block_channel_sums(sums + (long long)gg * Rg * f.C + c0, f.C, Rg, f.CB, red);
+        if (!w.owner && gg != w.g) continue;                       // (uniform per workgroup)
+        block_channel_sums(sums + (long long)gg * Rg * f.C + w.c0, f.C, Rg, f.CB, red);
         if (tid < f.CB) {
-            const int c = c0 + tid;
-            const double s1 = red[tid][0], s2 = red[tid][1];
-            const double cnt = count > 0.0 ? count : (double)f.Ng * inner;
-            const double mean = s1 / cnt;
-            double var = s2 / cnt - mean * mean;
-            if (var < 0.0) var = 0.0;
-            const float rstd = (float)(1.0 / sqrt(var + (double)eps));
-            const float ga = gamma ? gamma[c] : 1.f, be = beta ? beta[c] : 0.f;
-            const float scale = ga * rstd, shift = be - (float)mean * scale;
-            if (gg == g) {
-                mine[tid][0] = scale;
-                mine[tid][1] = shift;
-            }
-            if (owner) {
-                const int ci = gg * f.C + c;
-                coef[ci] = scale;
-                coef[NC + ci] = shift;
-                coef[2 * NC + ci] = (float)mean;
-                coef[3 * NC + ci] = rstd;
-                if (running_mean) {
-                    const double unbiased = cnt > 1.0 ? var * cnt / (cnt - 1.0) : var;
-                    running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * (float)mean;
-                    running_var[c] = (1.f - momentum) * running_var[c] + momentum * (float)unbiased;
-                }
+            const int c = w.c0 + tid;
+            const Coef k = bn_finalize(red[tid][0], red[tid][1], bn_count(count, f.Ng, inner), gamma, beta, eps, c,
+                                       gg * f.C + c, w.owner, o);
+            if (gg == w.g) {
+                mine[tid][0] = k.sc;
+                mine[tid][1] = k.sh;
             }
         }
     }
-    if (owner && c0 == 0 && tid == 0 && nbt) *nbt += f.groups;
+    if (w.owner && w.c0 == 0 && tid == 0 && nbt) *nbt += f.groups;
     __syncthreads();
-    const int n0 = g * f.Ng + s * f.P;
-    const int n1 = min(g * f.Ng + f.Ng, n0 + f.P);
-    const int total = (n1 - n0) * f.run4;
-    const f32x4* __restrict__ x4 = reinterpret_cast<const f32x4*>(x);
-    f32x4* __restrict__ o4 = reinterpret_cast<f32x4*>(out);
-    for (int i = tid; i < total; i += PW_THREADS) {
-        const uint32_t p = fdiv((uint32_t)i, f.div_run);
-        const uint32_t rem = (uint32_t)i - p * (uint32_t)f.run4;
-        const uint32_t cb = fdiv(rem, f.div_q4);
-        const long long idx = ((long long)(n0 + (int)p) * f.C + c0) * f.q4 + rem;
+    const BnSliceWalk sw = bn_slice_walk(f, w);
+    for (const int i : sw.is) {
+        const SliceAt at = slice_at(f, sw, i);
+        const long long idx = at.idx;
+        const uint32_t cb = at.cb;
         const float sc = mine[cb][0], sh = mine[cb][1];
-        const f32x4 v = x4[idx];
-        f32x4 o;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) o[k] = act_fwd(v[k] * sc + sh, act, slope);
-        o4[idx] = o;
+        st4(out, idx, norm_act4(ld4(x, idx), sc, sh, act, slope));
     }
 }
 
 // Per-row statistics, their finalize and the apply in ONE launch (InstanceNorm / AdaIN; round 2): the sub-wave that
-// summed a row turns the sums into (scale, shift, mean, rstd) itself (gamma / beta per channel, per row, or per row
-// from a packed [N][2C] array: affine_per_row 0 / 1 / 2; unbiased = 1 uses var * n/(n-1)) and streams the row again while it is still in this CU's cache.  Replaces row_sums + row_finalize +
+// summed a row turns the sums into (scale, shift, mean, rstd) itself (gamma / beta by affine_index; unbiased = 1 uses
+// var * n/(n-1)) and streams the row again while it is still in this CU's cache.  Replaces row_sums + row_finalize +
 // norm_act_apply: HoloGAN ran 25 such triples per optimizer-step pair, each launch costing its ~2.5 us dispatch gap
 // on top of ~5 us of work.
 // CACHE > 0: a lane keeps its (at most CACHE) float4 of the row in registers, so the row is read from memory once;
@@ -338,16 +526,14 @@ __global__ __launch_bounds__(PW_THREADS) void rownorm_act_fused_kernel(const flo
                                                                        int unbiased, int act, float slope,
                                                                        int x_rows, const float* __restrict__ sigma,
                                                                        int sigma_rows) {
-    const int lane = threadIdx.x & 63;
-    const int wave = (blockIdx.x * PW_THREADS + threadIdx.x) >> 6;
-    const int nwaves = (gridDim.x * PW_THREADS) >> 6;
-    const int sub = lane / g.lpr, l = lane % g.lpr;
-    for (long long row0 = (long long)wave * g.rpw; row0 < g.rows; row0 += (long long)nwaves * g.rpw) {
-        const long long row = row0 + sub;
+    const RowWalk w = row_walk(g);
+    for (const long long row0 : w.row0s) {
+        const long long row = row0 + w.sub;
         const bool live = row < g.rows;
+        const int l = w.l;
         // x_rows > 0: x has only x_rows rows, shared by every sample (HoloGAN's learned constant, which the reference
         // materialises with .repeat(batch, ...), hologan_generator.py:141)
-        const f32x4* p = reinterpret_cast<const f32x4*>(x) + (x_rows > 0 ? row % x_rows : row) * g.q4;
+        const f32x4* p = row_ptr(x, x_rows > 0 ? row % x_rows : row, g);
         // Two passes over the (cache-resident) row: the mean first, then the centred second moment with the
         // correction term of the "corrected two-pass" formula.  The one-pass E[x^2] - mean^2 of row_sums_kernel loses
         // mean^2 / var digits, and AdaIN rows do have |mean| >> sigma (a convolution of an all-positive, nearly
@@ -363,7 +549,7 @@ __global__ __launch_bounds__(PW_THREADS) void rownorm_act_fused_kernel(const flo
                 s[0] += (c[i].x + c[i].y) + (c[i].z + c[i].w);
             }
         } else if (live) {
-            for (int q = l; q < g.q4; q += g.lpr) {
+            for (const int q : lane_q4s(g, true, l)) {
                 f32x4 v = p[q];
                 s[0] += (v.x + v.y) + (v.z + v.w);
             }
@@ -377,21 +563,21 @@ __global__ __launch_bounds__(PW_THREADS) void rownorm_act_fused_kernel(const flo
             for (int i = 0; i < CACHE; ++i) {
                 if (live && l + i * g.lpr < g.q4) {
 #pragma unroll
-                    for (int k = 0; k < 4; ++k) {
-                        const float e = c[i][k] - mean_f;
-                        d[0] += e;
-                        d[1] += e * e;
+                    for (int e = 0; e < 4; ++e) {
+                        const float t = c[i][e] - mean_f;
+                        d[0] += t;
+                        d[1] += t * t;
                     }
                 }
             }
         } else if (live) {
-            for (int q = l; q < g.q4; q += g.lpr) {
+            for (const int q : lane_q4s(g, true, l)) {
                 f32x4 v = p[q];
 #pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const float e = v[k] - mean_f;
-                    d[0] += e;
-                    d[1] += e * e;
+                for (int e = 0; e < 4; ++e) {
+                    const float t = v[e] - mean_f;
+                    d[0] += t;
+                    d[1] += t * t;
                 }
             }
         }
@@ -410,17 +596,14 @@ __global__ __launch_bounds__(PW_THREADS) void rownorm_act_fused_kernel(const flo
             const float sg = sigma[r / sigma_rows];
             eps_r = eps * sg * sg;
         }
-        const float rstd = (float)(1.0 / sqrt(var + (double)eps_r));
-        const int gi = affine_per_row == 2 ? (r / C) * 2 * C + r % C : (affine_per_row ? r : r % C);
+        Coef k;
+        k.rstd = (float)(1.0 / sqrt(var + (double)eps_r));
+        const int gi = affine_index(r, C, affine_per_row);
         const float ga = gamma ? gamma[gi] : 1.f, be = beta ? beta[gi] : 0.f;
-        const float sc = ga * rstd;
-        const float sh = be - (float)mean * sc;
-        if (l == 0) {
-            coef[r] = sc;
-            coef[g.rows + r] = sh;
-            coef[2 * g.rows + r] = (float)mean;
-            coef[3 * g.rows + r] = rstd;
-        }
+        k.sc = ga * k.rstd;
+        k.sh = be - (float)mean * k.sc;
+        k.mean = (float)mean;
+        if (l == 0) store_coef(coef, g.rows, r, k);
         if (!out) continue;       // statistics only (gz_rownorm_stats)
         f32x4* po = reinterpret_cast<f32x4*>(out) + row * g.q4;
         if constexpr (CACHE > 0) {
@@ -430,15 +613,15 @@ __global__ __launch_bounds__(PW_THREADS) void rownorm_act_fused_kernel(const flo
                 if (q < g.q4) {
                     f32x4 o;
 #pragma unroll
-                    for (int k = 0; k < 4; ++k) o[k] = act_fwd(c[i][k] * sc + sh, act, slope);
+                    for (int e = 0; e < 4; ++e) o[e] = act_fwd(c[i][e] * k.sc + k.sh, act, slope);
                     po[q] = o;
                 }
             }
         } else {
-            for (int q = l; q < g.q4; q += g.lpr) {
+            for (const int q : lane_q4s(g, true, l)) {
                 f32x4 v = p[q], o;
 #pragma unroll
-                for (int k = 0; k < 4; ++k) o[k] = act_fwd(v[k] * sc + sh, act, slope);
+                for (int e = 0; e < 4; ++e) o[e] = act_fwd(v[e] * k.sc + k.sh, act, slope);
                 po[q] = o;
             }
         }
@@ -446,85 +629,75 @@ __global__ __launch_bounds__(PW_THREADS) void rownorm_act_fused_kernel(const flo
 }
 
 // ---------------------------------------------------------------------------
-// first backward
-//   z = x*scale + shift, dz = gout * act'(z), xh = (x - mean) * rstd
-//   rowsums: (sum dz, sum dz*xh)
-//   dx = scale * (dz - k1 - xh*k2),  k1 = mean(dz), k2 = mean(dz*xh) over the statistics group
+// first backward (element terms: bwd_terms, bwd_dx above);  rowsums: (sum dz, sum dz*xh)
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ float act_grad_z(float z, int act, float slope) {
-    if (act == ACT_RELU) return z > 0.f ? 1.f : 0.f;
-    if (act == ACT_LRELU) return z > 0.f ? 1.f : slope;
-    return 1.f;
-}
-
 __global__ __launch_bounds__(PW_THREADS) void norm_bwd_rowsums_kernel(const float* __restrict__ gout,
                                                                       const float* __restrict__ x,
                                                                       const float* __restrict__ coef,
                                                                       f32x2* __restrict__ sums, RowGeom g, int C,
                                                                       int per_channel, int ncoef, int act,
                                                                       float slope, int group_rows) {
-    const int lane = threadIdx.x & 63;
-    const int wave = (blockIdx.x * PW_THREADS + threadIdx.x) >> 6;
-    const int nwaves = (gridDim.x * PW_THREADS) >> 6;
-    const int sub = lane / g.lpr, l = lane % g.lpr;
-    for (long long row0 = (long long)wave * g.rpw; row0 < g.rows; row0 += (long long)nwaves * g.rpw) {
-        long long row = row0 + sub;
+    const RowWalk w = row_walk(g);
+    for (const long long row0 : w.row0s) {
+        const long long row = row0 + w.sub;
+        const bool live = row < g.rows;
+        const int l = w.l;
         float s[2] = {0.f, 0.f};
-        if (row < g.rows) {
-            int ci = per_channel ? (int)(row % C) + (group_rows ? (int)(row / group_rows) * C : 0) : (int)row;
-            float sc = coef[ci], sh = coef[ncoef + ci], mean = coef[2 * ncoef + ci], rstd = coef[3 * ncoef + ci];
-            const f32x4* px = reinterpret_cast<const f32x4*>(x) + row * g.q4;
-            const f32x4* pg = reinterpret_cast<const f32x4*>(gout) + row * g.q4;
-            for (int q = l; q < g.q4; q += g.lpr) {
-                f32x4 xv = px[q], gv = pg[q];
+        if (live) {
+            const Coef k = load_coef(coef, ncoef, row_coef_index(row, C, per_channel, group_rows));
+            const f32x4 *px = row_ptr(x, row, g), *pg = row_ptr(gout, row, g);
+            for (const int q : lane_q4s(g, live, l)) {
+                const f32x4 xv = px[q], gv = pg[q];
 #pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    float dz = gv[k] * act_grad_z(xv[k] * sc + sh, act, slope);
-                    s[0] += dz;
-                    s[1] += dz * ((xv[k] - mean) * rstd);
+                for (int e = 0; e < 4; ++e) {
+                    const BwdTerms t = bwd_terms(xv[e], gv[e], k, act, slope);
+                    s[0] += t.dz;
+                    s[1] += t.dz * t.xh;
                 }
             }
         }
         sub_reduce<2>(s, g.lpr);
-        if (row < g.rows && l == 0) sums[row] = f32x2{s[0], s[1]};
+        if (live && l == 0) sums[row] = f32x2{s[0], s[1]};
     }
 }
 
-// BatchNorm: combine row sums over n -> k[0*C] = mean(dz), k[1*C] = mean(dz*xh); dgamma, dbeta.
-// One wavefront per channel.
-// (statistics groups: k per (group, channel); the affine gradients sum over the groups.  accumulate != 0: dgamma /
-// dbeta already hold earlier contributions -- the gradient sink of functional/_base.py -- and are added to)
+// BatchNorm: combine row sums over n -> k[0*C] = mean(dz), k[1*C] = mean(dz*xh) per (group, channel) when k is there;
+// dgamma, dbeta summed over the groups.  One wavefront per channel.  The body of bn_bwd_finalize_kernel, and -- with
+// one group and no k -- of row_bwd_affine_kernel.
+__device__ __forceinline__ void channel_bwd_finalize(const f32x2* __restrict__ sums, float* __restrict__ k,
+                                                     float* __restrict__ dgamma, float* __restrict__ dbeta, int N,
+                                                     int C, int inner, int groups, int accumulate) {
+    const int c = blockIdx.x, lane = threadIdx.x;
+    const int Ng = N / groups;
+    AffineSums t;
+    for (int g = 0; g < groups; ++g) {
+        double s1, s2;
+        column_sums(sums, g * Ng, Ng, C, c, lane, 64, s1, s2);
+        bn_bwd_k(s1, s2, (double)Ng * inner, k, groups * C, g * C + c, lane == 0, t);
+    }
+    if (lane == 0) affine_grad_store(dgamma, dbeta, c, t, accumulate);
+}
+
 __global__ __launch_bounds__(64) void bn_bwd_finalize_kernel(const f32x2* __restrict__ sums, float* __restrict__ k,
                                                              float* __restrict__ dgamma, float* __restrict__ dbeta,
                                                              int N, int C, int inner, int groups, int accumulate) {
-    const int c = blockIdx.x, lane = threadIdx.x;
-    const int Ng = N / groups, NC = groups * C;
-    double t1 = 0.0, t2 = 0.0;
-    for (int g = 0; g < groups; ++g) {
-        double s1 = 0.0, s2 = 0.0;
-        for (int n = lane; n < Ng; n += 64) {
-            f32x2 v = sums[(long long)(g * Ng + n) * C + c];
-            s1 += (double)v.x;
-            s2 += (double)v.y;
-        }
-        s1 = wave_sum_d(s1);
-        s2 = wave_sum_d(s2);
-        if (lane == 0) {
-            double cnt = (double)Ng * inner;
-            k[g * C + c] = (float)(s1 / cnt);
-            k[NC + g * C + c] = (float)(s2 / cnt);
-        }
-        t1 += s1;
-        t2 += s2;
-    }
-    if (lane != 0) return;
-    if (dgamma) dgamma[c] = (accumulate ? dgamma[c] : 0.f) + (float)t2;
-    if (dbeta) dbeta[c] = (accumulate ? dbeta[c] : 0.f) + (float)t1;
+    channel_bwd_finalize(sums, k, dgamma, dbeta, N, C, inner, groups, accumulate);
+}
+
+// per-channel affine over per-row statistics (InstanceNorm): dgamma[c] = sum_n s2[n,c], dbeta[c] = sum_n s1[n,c]
+__global__ __launch_bounds__(64) void row_bwd_affine_kernel(const f32x2* __restrict__ sums,
+                                                            float* __restrict__ dgamma, float* __restrict__ dbeta,
+                                                            int N, int C, int accumulate = 0) {
+    channel_bwd_finalize(sums, nullptr, dgamma, dbeta, N, C, 1, 1, accumulate);
 }
 
 // per-row statistics: k = sums / inner (and per-row dgamma / dbeta for AdaIN-style affine)
 // With the unbiased variance (AdaIN) d xh_i/d x_j = rstd (delta_ij - 1/n - xh_i xh_j / (n-1)), hence the
 // second coefficient is sum(dz*xh) / (n-1).
+__device__ __forceinline__ f32x2 row_bwd_k(float s1, float s2, int inner, int unbiased) {
+    return f32x2{s1 / (float)inner, s2 / (float)((unbiased && inner > 1) ? inner - 1 : inner)};
+}
+
 __global__ void row_bwd_finalize_kernel(const f32x2* __restrict__ sums, float* __restrict__ k,
                                         float* __restrict__ dgamma, float* __restrict__ dbeta, int N, int C,
                                         int inner, int affine_per_row, int unbiased) {
@@ -532,32 +705,15 @@ __global__ void row_bwd_finalize_kernel(const f32x2* __restrict__ sums, float* _
     int rows = N * C;
     if (i < rows) {
         f32x2 v = sums[i];
-        k[i] = v.x / (float)inner;
-        k[rows + i] = v.y / (float)((unbiased && inner > 1) ? inner - 1 : inner);
+        const f32x2 kk = row_bwd_k(v.x, v.y, inner, unbiased);
+        k[i] = kk.x;
+        k[rows + i] = kk.y;
         if (affine_per_row) {
-            const int gi = affine_per_row == 2 ? (i / C) * 2 * C + i % C : i;     // 2: packed [N][2C] gradient
+            const int gi = affine_index(i, C, affine_per_row);
             if (dgamma) dgamma[gi] = v.y;
             if (dbeta) dbeta[gi] = v.x;
         }
     }
-}
-
-// per-channel affine over per-row statistics (InstanceNorm): dgamma[c] = sum_n s2[n,c], dbeta[c] = sum_n s1[n,c]
-__global__ __launch_bounds__(64) void row_bwd_affine_kernel(const f32x2* __restrict__ sums,
-                                                            float* __restrict__ dgamma, float* __restrict__ dbeta,
-                                                            int N, int C, int accumulate = 0) {
-    const int c = blockIdx.x, lane = threadIdx.x;
-    double s1 = 0.0, s2 = 0.0;
-    for (int n = lane; n < N; n += 64) {
-        f32x2 v = sums[(long long)n * C + c];
-        s1 += (double)v.x;
-        s2 += (double)v.y;
-    }
-    s1 = wave_sum_d(s1);
-    s2 = wave_sum_d(s2);
-    if (lane != 0) return;
-    if (dgamma) dgamma[c] = (accumulate ? dgamma[c] : 0.f) + (float)s2;
-    if (dbeta) dbeta[c] = (accumulate ? dbeta[c] : 0.f) + (float)s1;
 }
 
 __global__ __launch_bounds__(PW_THREADS) void norm_bwd_apply_kernel(const float* __restrict__ gout,
@@ -566,21 +722,18 @@ __global__ __launch_bounds__(PW_THREADS) void norm_bwd_apply_kernel(const float*
                                                                     const float* __restrict__ k,
                                                                     float* __restrict__ dx, ApplyGeom g, int act,
                                                                     float slope) {
-    const long long stride = (long long)gridDim.x * PW_THREADS;
-    for (long long i = (long long)blockIdx.x * PW_THREADS + threadIdx.x; i < g.total4; i += stride) {
-        int ci = coef_index(i, g);
-        float sc = coef[ci], sh = coef[g.ncoef + ci], mean = coef[2 * g.ncoef + ci], rstd = coef[3 * g.ncoef + ci];
-        float k1 = k[ci], k2 = k[g.ncoef + ci];
-        f32x4 xv = reinterpret_cast<const f32x4*>(x)[i];
-        f32x4 gv = reinterpret_cast<const f32x4*>(gout)[i];
+    for (const long long i : ew4_range(g.total4)) {
+        const int ci = coef_index(i, g);
+        const Coef c = load_coef(coef, g.ncoef, ci);
+        const float k1 = k[ci], k2 = k[g.ncoef + ci];
+        const f32x4 xv = ld4(x, i), gv = ld4(gout, i);
         f32x4 o;
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-            float dz = gv[q] * act_grad_z(xv[q] * sc + sh, act, slope);
-            float xh = (xv[q] - mean) * rstd;
-            o[q] = sc * (dz - k1 - xh * k2);
+            const BwdTerms t = bwd_terms(xv[q], gv[q], c, act, slope);
+            o[q] = bwd_dx(c.sc, t.dz, t.xh, k1, k2);
         }
-        reinterpret_cast<f32x4*>(dx)[i] = o;
+        st4(dx, i, o);
     }
 }
 
@@ -594,63 +747,46 @@ __global__ __launch_bounds__(PW_THREADS) void bn_bwd_apply_fused_kernel(
     __shared__ double red[PW_THREADS][2];
     __shared__ float mine[16][6];          // k1, k2, scale, shift, mean, rstd
     const int tid = threadIdx.x;
-    const int s = blockIdx.x % f.S, bg = blockIdx.x / f.S, g = bg % f.groups, c0 = (bg / f.groups) * f.CB;
-    const bool owner = g == 0 && s == 0;
+    const BnSlice w = bn_slice(f);
     const int NC = f.groups * f.C;
-    double t1 = 0.0, t2 = 0.0;
+    AffineSums t;
     for (int gg = 0; gg < f.groups; ++gg) {
-        if (!owner && gg != g) continue;
-        block_channel_sums(sums + (long long)gg * f.Ng * f.C + c0, f.C, f.Ng, f.CB, red);
+        if (!w.owner && gg != w.g) continue;
+        block_channel_sums(sums + (long long)gg * f.Ng * f.C + w.c0, f.C, f.Ng, f.CB, red);
         if (tid < f.CB) {
-            const double s1 = red[tid][0], s2 = red[tid][1];
-            const double cnt = (double)f.Ng * inner;
-            const float k1 = (float)(s1 / cnt), k2 = (float)(s2 / cnt);
-            if (gg == g) {
-                mine[tid][0] = k1;
-                mine[tid][1] = k2;
+            const f32x2 k = bn_bwd_k(red[tid][0], red[tid][1], (double)f.Ng * inner, kout, NC, gg * f.C + w.c0 + tid,
+                                     w.owner, t);
+            if (gg == w.g) {
+                mine[tid][0] = k.x;
+                mine[tid][1] = k.y;
             }
-            if (owner && kout) {
-                kout[gg * f.C + c0 + tid] = k1;
-                kout[NC + gg * f.C + c0 + tid] = k2;
-            }
-            t1 += s1;
-            t2 += s2;
         }
     }
     if (tid < f.CB) {
-        const int c = c0 + tid, ci = g * f.C + c;
-        if (owner) {
-            if (dgamma) dgamma[c] = (accumulate ? dgamma[c] : 0.f) + (float)t2;
-            if (dbeta) dbeta[c] = (accumulate ? dbeta[c] : 0.f) + (float)t1;
-        }
-        mine[tid][2] = coef[ci];
-        mine[tid][3] = coef[NC + ci];
-        mine[tid][4] = coef[2 * NC + ci];
-        mine[tid][5] = coef[3 * NC + ci];
+        const int c = w.c0 + tid;
+        if (w.owner) affine_grad_store(dgamma, dbeta, c, t, accumulate);
+        const Coef k = load_coef(coef, NC, w.g * f.C + c);
+        mine[tid][2] = k.sc;
+        mine[tid][3] = k.sh;
+        mine[tid][4] = k.mean;
+        mine[tid][5] = k.rstd;
     }
     __syncthreads();
-    const int n0 = g * f.Ng + s * f.P;
-    const int n1 = min(g * f.Ng + f.Ng, n0 + f.P);
-    const int total = (n1 - n0) * f.run4;
-    const f32x4* __restrict__ x4 = reinterpret_cast<const f32x4*>(x);
-    const f32x4* __restrict__ g4 = reinterpret_cast<const f32x4*>(gout);
-    f32x4* __restrict__ d4 = reinterpret_cast<f32x4*>(dx);
-    for (int i = tid; i < total; i += PW_THREADS) {
-        const uint32_t p = fdiv((uint32_t)i, f.div_run);
-        const uint32_t rem = (uint32_t)i - p * (uint32_t)f.run4;
-        const uint32_t cb = fdiv(rem, f.div_q4);
-        const long long idx = ((long long)(n0 + (int)p) * f.C + c0) * f.q4 + rem;
-        const float k1 = mine[cb][0], k2 = mine[cb][1], sc = mine[cb][2], sh = mine[cb][3], mean = mine[cb][4],
-                    rstd = mine[cb][5];
-        const f32x4 xv = x4[idx], gv = g4[idx];
+    const BnSliceWalk sw = bn_slice_walk(f, w);
+    for (const int i : sw.is) {
+        const SliceAt at = slice_at(f, sw, i);
+        const long long idx = at.idx;
+        const uint32_t cb = at.cb;
+        const float k1 = mine[cb][0], k2 = mine[cb][1];
+        const Coef c = {mine[cb][2], mine[cb][3], mine[cb][4], mine[cb][5]};
+        const f32x4 xv = ld4(x, idx), gv = ld4(gout, idx);
         f32x4 o;
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-            const float dz = gv[q] * act_grad_z(xv[q] * sc + sh, act, slope);
-            const float xh = (xv[q] - mean) * rstd;
-            o[q] = sc * (dz - k1 - xh * k2);
+            const BwdTerms e = bwd_terms(xv[q], gv[q], c, act, slope);
+            o[q] = bwd_dx(c.sc, e.dz, e.xh, k1, k2);
         }
-        d4[idx] = o;
+        st4(dx, idx, o);
     }
 }
 
@@ -667,17 +803,14 @@ __global__ __launch_bounds__(PW_THREADS) void rownorm_bwd_fused_kernel(const flo
                                                                        f32x2* __restrict__ sums, RowGeom g, int C,
                                                                        int inner, int affine_per_row, int unbiased,
                                                                        int act, float slope) {
-    const int lane = threadIdx.x & 63;
-    const int wave = (blockIdx.x * PW_THREADS + threadIdx.x) >> 6;
-    const int nwaves = (gridDim.x * PW_THREADS) >> 6;
-    const int sub = lane / g.lpr, l = lane % g.lpr;
-    for (long long row0 = (long long)wave * g.rpw; row0 < g.rows; row0 += (long long)nwaves * g.rpw) {
-        const long long row = row0 + sub;
+    const RowWalk w = row_walk(g);
+    for (const long long row0 : w.row0s) {
+        const long long row = row0 + w.sub;
         const bool live = row < g.rows;
-        const int ci = live ? (int)row : 0;
-        const float sc = coef[ci], sh = coef[g.rows + ci], mean = coef[2 * g.rows + ci], rstd = coef[3 * g.rows + ci];
-        const f32x4* px = reinterpret_cast<const f32x4*>(x) + row * g.q4;
-        const f32x4* pg = reinterpret_cast<const f32x4*>(gout) + row * g.q4;
+        const int l = w.l;
+        const Coef k = load_coef(coef, g.rows, live ? (int)row : 0);
+        const f32x4* px = row_ptr(x, row, g);
+        const f32x4* pg = row_ptr(gout, row, g);
         float s[2] = {0.f, 0.f};
         f32x4 cdz[CACHE > 0 ? CACHE : 1], cxh[CACHE > 0 ? CACHE : 1];
         if constexpr (CACHE > 0) {
@@ -688,35 +821,32 @@ __global__ __launch_bounds__(PW_THREADS) void rownorm_bwd_fused_kernel(const flo
                 const f32x4 xv = in ? px[q] : f32x4{0.f, 0.f, 0.f, 0.f};
                 const f32x4 gv = in ? pg[q] : f32x4{0.f, 0.f, 0.f, 0.f};     // gv = 0: nothing added to the sums
 #pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const float dz = gv[k] * act_grad_z(xv[k] * sc + sh, act, slope);
-                    const float xh = (xv[k] - mean) * rstd;
-                    cdz[i][k] = dz;
-                    cxh[i][k] = xh;
-                    s[0] += dz;
-                    s[1] += dz * xh;
+                for (int e = 0; e < 4; ++e) {
+                    const BwdTerms t = bwd_terms(xv[e], gv[e], k, act, slope);
+                    cdz[i][e] = t.dz;
+                    cxh[i][e] = t.xh;
+                    s[0] += t.dz;
+                    s[1] += t.dz * t.xh;
                 }
             }
         } else if (live) {
-            for (int q = l; q < g.q4; q += g.lpr) {
+            for (const int q : lane_q4s(g, true, l)) {
                 f32x4 xv = px[q], gv = pg[q];
 #pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    float dz = gv[k] * act_grad_z(xv[k] * sc + sh, act, slope);
-                    s[0] += dz;
-                    s[1] += dz * ((xv[k] - mean) * rstd);
+                for (int e = 0; e < 4; ++e) {
+                    const BwdTerms t = bwd_terms(xv[e], gv[e], k, act, slope);
+                    s[0] += t.dz;
+                    s[1] += t.dz * t.xh;
                 }
             }
         }
         sub_reduce<2>(s, g.lpr);
         if (!live) continue;
-        const float k1 = s[0] / (float)inner;
-        const float k2 = s[1] / (float)((unbiased && inner > 1) ? inner - 1 : inner);
+        const f32x2 kk = row_bwd_k(s[0], s[1], inner, unbiased);
         if (l == 0) {
             if (sums) sums[row] = f32x2{s[0], s[1]};
             if (affine_per_row) {
-                const int r = (int)row;
-                const int gi = affine_per_row == 2 ? (r / C) * 2 * C + r % C : r;
+                const int gi = affine_index((int)row, C, affine_per_row);
                 if (dgamma) dgamma[gi] = s[1];
                 if (dbeta) dbeta[gi] = s[0];
             }
@@ -730,18 +860,17 @@ __global__ __launch_bounds__(PW_THREADS) void rownorm_bwd_fused_kernel(const flo
                 if (q < g.q4) {
                     f32x4 o;
 #pragma unroll
-                    for (int k = 0; k < 4; ++k) o[k] = sc * (cdz[i][k] - k1 - cxh[i][k] * k2);
+                    for (int e = 0; e < 4; ++e) o[e] = bwd_dx(k.sc, cdz[i][e], cxh[i][e], kk.x, kk.y);
                     po[q] = o;
                 }
             }
         } else {
-            for (int q = l; q < g.q4; q += g.lpr) {
+            for (const int q : lane_q4s(g, true, l)) {
                 f32x4 xv = px[q], gv = pg[q], o;
 #pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    float dz = gv[k] * act_grad_z(xv[k] * sc + sh, act, slope);
-                    float xh = (xv[k] - mean) * rstd;
-                    o[k] = sc * (dz - k1 - xh * k2);
+                for (int e = 0; e < 4; ++e) {
+                    const BwdTerms t = bwd_terms(xv[e], gv[e], k, act, slope);
+                    o[e] = bwd_dx(k.sc, t.dz, t.xh, kk.x, kk.y);
                 }
                 po[q] = o;
             }
@@ -765,7 +894,7 @@ __global__ __launch_bounds__(PW_THREADS) void adain_const_bwd_kernel(const float
     const int c = blockIdx.x;
     const int grp = threadIdx.x / g.lpr, l = threadIdx.x % g.lpr, groups = PW_THREADS / g.lpr;
     const int rows = N * C;
-    const f32x4* px = reinterpret_cast<const f32x4*>(x) + (long long)c * g.q4;
+    const f32x4* px = row_ptr(x, c, g);
     f32x4 xv[CACHE], acc[CACHE];
 #pragma unroll
     for (int i = 0; i < CACHE; ++i) {
@@ -775,8 +904,8 @@ __global__ __launch_bounds__(PW_THREADS) void adain_const_bwd_kernel(const float
     }
     for (int n = grp; n < N; n += groups) {
         const int r = n * C + c;
-        const float sc = coef[r], sh = coef[rows + r], mean = coef[2 * rows + r], rstd = coef[3 * rows + r];
-        const f32x4* pg = reinterpret_cast<const f32x4*>(gout) + (long long)r * g.q4;
+        const Coef k = load_coef(coef, rows, r);
+        const f32x4* pg = row_ptr(gout, r, g);
         f32x4 dz[CACHE], xh[CACHE];
         float s[2] = {0.f, 0.f};
 #pragma unroll
@@ -784,15 +913,16 @@ __global__ __launch_bounds__(PW_THREADS) void adain_const_bwd_kernel(const float
             const int q = l + i * g.lpr;
             const f32x4 gv = q < g.q4 ? pg[q] : f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                dz[i][k] = gv[k] * act_grad_z(xv[i][k] * sc + sh, act, slope);
-                xh[i][k] = (xv[i][k] - mean) * rstd;
-                s[0] += dz[i][k];
-                s[1] += dz[i][k] * xh[i][k];
+            for (int e = 0; e < 4; ++e) {
+                const BwdTerms t = bwd_terms(xv[i][e], gv[e], k, act, slope);
+                dz[i][e] = t.dz;
+                xh[i][e] = t.xh;
+                s[0] += dz[i][e];
+                s[1] += dz[i][e] * xh[i][e];
             }
         }
         sub_reduce<2>(s, g.lpr);
-        const float k1 = s[0] / (float)inner, k2 = s[1] / (float)(inner > 1 ? inner - 1 : inner);
+        const f32x2 kk = row_bwd_k(s[0], s[1], inner, 1);
         if (l == 0) {
             dsb[(long long)n * 2 * C + c] = s[1];
             dsb[(long long)n * 2 * C + C + c] = s[0];
@@ -800,7 +930,7 @@ __global__ __launch_bounds__(PW_THREADS) void adain_const_bwd_kernel(const float
 #pragma unroll
         for (int i = 0; i < CACHE; ++i)
 #pragma unroll
-            for (int k = 0; k < 4; ++k) acc[i][k] += sc * (dz[i][k] - k1 - xh[i][k] * k2);
+            for (int e = 0; e < 4; ++e) acc[i][e] += bwd_dx(k.sc, dz[i][e], xh[i][e], kk.x, kk.y);
     }
 #pragma unroll
     for (int i = 0; i < CACHE; ++i) {
@@ -833,35 +963,30 @@ __global__ __launch_bounds__(PW_THREADS) void norm_bwd2_rowsums_kernel(const flo
                                                                        const float* __restrict__ coef,
                                                                        Sums5* __restrict__ sums, RowGeom g,
                                                                        int act, float slope) {
-    const int lane = threadIdx.x & 63;
-    const int wave = (blockIdx.x * PW_THREADS + threadIdx.x) >> 6;
-    const int nwaves = (gridDim.x * PW_THREADS) >> 6;
-    const int sub = lane / g.lpr, l = lane % g.lpr;
-    const int ncoef = g.rows;
-    for (long long row0 = (long long)wave * g.rpw; row0 < g.rows; row0 += (long long)nwaves * g.rpw) {
-        long long row = row0 + sub;
+    const RowWalk w = row_walk(g);
+    for (const long long row0 : w.row0s) {
+        const long long row = row0 + w.sub;
+        const bool live = row < g.rows;
+        const int l = w.l;
         float s[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
-        if (row < g.rows) {
-            float sc = coef[row], sh = coef[ncoef + row], mean = coef[2 * ncoef + row], rstd = coef[3 * ncoef + row];
-            const f32x4* px = reinterpret_cast<const f32x4*>(x) + row * g.q4;
-            const f32x4* pg = reinterpret_cast<const f32x4*>(gout) + row * g.q4;
-            const f32x4* pv = reinterpret_cast<const f32x4*>(v) + row * g.q4;
-            for (int q = l; q < g.q4; q += g.lpr) {
-                f32x4 xv = px[q], gv = pg[q], vv = pv[q];
+        if (live) {
+            const Coef k = load_coef(coef, g.rows, (int)row);
+            const f32x4 *px = row_ptr(x, row, g), *pg = row_ptr(gout, row, g), *pv = row_ptr(v, row, g);
+            for (const int q : lane_q4s(g, live, l)) {
+                const f32x4 xv = px[q], gv = pg[q], vv = pv[q];
 #pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    float gz = gv[k] * act_grad_z(xv[k] * sc + sh, act, slope);
-                    float xh = (xv[k] - mean) * rstd;
-                    s[0] += vv[k];
-                    s[1] += gz;
-                    s[2] += gz * xh;
-                    s[3] += vv[k] * xh;
-                    s[4] += vv[k] * gz;
+                for (int e = 0; e < 4; ++e) {
+                    const BwdTerms t = bwd_terms(xv[e], gv[e], k, act, slope);
+                    s[0] += vv[e];
+                    s[1] += t.dz;
+                    s[2] += t.dz * t.xh;
+                    s[3] += vv[e] * t.xh;
+                    s[4] += vv[e] * t.dz;
                 }
             }
         }
         sub_reduce<5>(s, g.lpr);
-        if (row < g.rows && l == 0) sums[row] = Sums5{s[0], s[1], s[2], s[3], s[4]};
+        if (live && l == 0) sums[row] = Sums5{s[0], s[1], s[2], s[3], s[4]};
     }
 }
 
@@ -869,29 +994,26 @@ __global__ __launch_bounds__(PW_THREADS) void norm_bwd2_apply_kernel(
     const float* __restrict__ gout, const float* __restrict__ v, const float* __restrict__ x,
     const float* __restrict__ coef, const Sums5* __restrict__ sums, float* __restrict__ gg_out,
     float* __restrict__ gx, ApplyGeom g, int act, float slope) {
-    const long long stride = (long long)gridDim.x * PW_THREADS;
     const float inv = 1.f / (float)(g.q4 * 4);
-    for (long long i = (long long)blockIdx.x * PW_THREADS + threadIdx.x; i < g.total4; i += stride) {
-        int r = (int)fdiv((uint32_t)i, g.div_q4);
-        float sc = coef[r], sh = coef[g.ncoef + r], mean = coef[2 * g.ncoef + r], rstd = coef[3 * g.ncoef + r];
+    for (const long long i : ew4_range(g.total4)) {
+        const int r = (int)fdiv((uint32_t)i, g.div_q4);
+        const Coef k = load_coef(coef, g.ncoef, r);
         Sums5 s = sums[r];
         float mv = s.v * inv, mg = s.g * inv, c = s.gx * inv, mvx = s.vx * inv, mvg = s.vg * inv;
         float t1 = mvg - mv * mg - c * mvx;
-        f32x4 xv = reinterpret_cast<const f32x4*>(x)[i];
-        f32x4 gv = reinterpret_cast<const f32x4*>(gout)[i];
-        f32x4 vv = reinterpret_cast<const f32x4*>(v)[i];
+        const f32x4 xv = ld4(x, i), gv = ld4(gout, i), vv = ld4(v, i);
         f32x4 o1, o2;
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-            float m = act_grad_z(xv[q] * sc + sh, act, slope);
-            float gz = gv[q] * m;
-            float xh = (xv[q] - mean) * rstd;
+            const float m = bwd_mask(xv[q], k, act, slope);
+            const float gz = gv[q] * m;
+            const float xh = (xv[q] - k.mean) * k.rstd;
             float pv = vv[q] - mv - xh * mvx;
-            o1[q] = m * sc * pv;
-            o2[q] = -sc * rstd * (xh * t1 + c * pv + mvx * (gz - mg - xh * c));
+            o1[q] = m * k.sc * pv;
+            o2[q] = -k.sc * k.rstd * (xh * t1 + c * pv + mvx * (gz - mg - xh * c));
         }
-        if (gg_out) reinterpret_cast<f32x4*>(gg_out)[i] = o1;
-        if (gx) reinterpret_cast<f32x4*>(gx)[i] = o2;
+        if (gg_out) st4(gg_out, i, o1);
+        if (gx) st4(gx, i, o2);
     }
 }
 
@@ -920,8 +1042,7 @@ __global__ __launch_bounds__(PW_THREADS) void act_bwd_kernel(const float* __rest
                                                              const float* __restrict__ out,
                                                              float* __restrict__ dx, long long total4, int act,
                                                              float slope) {
-    const long long stride = (long long)gridDim.x * PW_THREADS;
-    for (long long i = (long long)blockIdx.x * PW_THREADS + threadIdx.x; i < total4; i += stride) {
+    for (const long long i : ew4_range(total4)) {
         f32x4 gv = reinterpret_cast<const f32x4*>(g)[i];
         f32x4 ov = reinterpret_cast<const f32x4*>(out)[i];
         f32x4 o;
@@ -935,17 +1056,18 @@ __global__ __launch_bounds__(PW_THREADS) void act_bwd_kernel(const float* __rest
 __global__ __launch_bounds__(PW_THREADS) void tanh_bwd2_kernel(const float* __restrict__ v, const float* __restrict__ g,
                                                                const float* __restrict__ out, float* __restrict__ res,
                                                                long long total4) {
-    const long long stride = (long long)gridDim.x * PW_THREADS;
-    for (long long i = (long long)blockIdx.x * PW_THREADS + threadIdx.x; i < total4; i += stride) {
-        const f32x4 a = reinterpret_cast<const f32x4*>(v)[i], b = reinterpret_cast<const f32x4*>(g)[i];
-        const f32x4 o = reinterpret_cast<const f32x4*>(out)[i];
+    for (const long long i : ew4_range(total4)) {
+        const f32x4 a = ld4(v, i), b = ld4(g, i), o = ld4(out, i);
         f32x4 r;
 #pragma unroll
         for (int q = 0; q < 4; ++q) r[q] = a[q] * b[q] * (-2.f * o[q]);
-        reinterpret_cast<f32x4*>(res)[i] = r;
+        st4(res, i, r);
     }
 }
 
+// ---------------------------------------------------------------------------
+// launchers
+// ---------------------------------------------------------------------------
 static int ew_grid(long long total4) {
     long long b = (total4 + PW_THREADS - 1) / PW_THREADS;
     if (b > 256 * 8) b = 256 * 8;
@@ -974,19 +1096,98 @@ static bool norm_shape_ok(int N, int C, int inner) {
            (long long)N * C * inner / 4 < (1ll << 31);
 }
 
-static void launch_rownorm_fused(const float* x, const float* gamma, const float* beta, float* coef, float* out,
-                                 const RowGeom& g, int C, int inner, float eps, int affine_per_row, int unbiased,
-                                 int act, float slope, hipStream_t stream, int x_rows = 0,
-                                 const float* sigma = nullptr, int sigma_rows = 1) {
-    const int per_lane = (g.q4 + g.lpr - 1) / g.lpr;      // float4 per lane
-#define GZ_RN(CACHE)                                                                                               \
-    hipLaunchKernelGGL(rownorm_act_fused_kernel<CACHE>, dim3(row_grid(g)), dim3(PW_THREADS), 0, stream, x, gamma, \
-                       beta, coef, out, g, C, inner, eps, affine_per_row, unbiased, act, slope, x_rows, sigma, sigma_rows)
-    if (per_lane <= 1) GZ_RN(1);
-    else if (per_lane <= 4) GZ_RN(4);
-    else if (per_lane <= 16) GZ_RN(16);
-    else GZ_RN(0);
-#undef GZ_RN
+// The CACHE image of a row kernel for rows of `per_lane` float4 per lane: the smallest cache that holds them, up to
+// max_cache (the forward takes 16, the backward knobs().norm_bwd_cache); 0 = stream.
+static int cache_for(const RowGeom& g, int max_cache) {
+    const int per_lane = (g.q4 + g.lpr - 1) / g.lpr;
+    if (per_lane <= 1) return 1;
+    if (per_lane <= 4 && max_cache >= 4) return 4;
+    if (per_lane <= 16 && max_cache >= 16) return 16;
+    return 0;
+}
+
+// launch(std::integral_constant<int, CACHE>) for the image that `cache` names
+template <class Launch>
+static void with_cache(int cache, Launch&& launch) {
+    switch (cache) {
+        case 1: launch(std::integral_constant<int, 1>()); break;
+        case 4: launch(std::integral_constant<int, 4>()); break;
+        case 16: launch(std::integral_constant<int, 16>()); break;
+        default: launch(std::integral_constant<int, 0>()); break;
+    }
+}
+
+static void launch_row_sums(const float* x, void* workspace, int N, int C, int inner, hipStream_t stream) {
+    const RowGeom g = row_geom((long long)N * C, inner);
+    hipLaunchKernelGGL(row_sums_kernel, dim3(row_grid(g)), dim3(PW_THREADS), 0, stream, x, (f32x2*)workspace, g);
+}
+
+static void launch_rownorm_fused(const float* x, const float* gamma, const float* beta, float* coef, float* out, int N,
+                                 int C, int inner, float eps, int affine_per_row, int unbiased, int act, float slope,
+                                 hipStream_t stream, int x_rows = 0, const float* sigma = nullptr, int sigma_rows = 1) {
+    const RowGeom g = row_geom((long long)N * C, inner);
+    with_cache(cache_for(g, 16), [&](auto cache) {
+        hipLaunchKernelGGL(rownorm_act_fused_kernel<decltype(cache)::value>, dim3(row_grid(g)), dim3(PW_THREADS), 0,
+                           stream, x, gamma, beta, coef, out, g, C, inner, eps, affine_per_row, unbiased, act, slope,
+                           x_rows, sigma, sigma_rows);
+    });
+}
+
+static void launch_rownorm_bwd_fused(const float* gout, const float* x, const float* coef, float* dx, float* dgamma,
+                                     float* dbeta, f32x2* sums, int N, int C, int inner, int affine_per_row,
+                                     int unbiased, int act, float slope, hipStream_t stream) {
+    const RowGeom g = row_geom((long long)N * C, inner);
+    with_cache(cache_for(g, knobs().norm_bwd_cache), [&](auto cache) {
+        hipLaunchKernelGGL(rownorm_bwd_fused_kernel<decltype(cache)::value>, dim3(row_grid(g)), dim3(PW_THREADS), 0,
+                           stream, gout, x, coef, dx, dgamma, dbeta, sums, g, C, inner, affine_per_row, unbiased, act,
+                           slope);
+    });
+}
+
+static int norm_act_bwd_impl(const float* gout, const float* x, const float* coef, float* dx, float* dgamma, float* dbeta,
+                             void* workspace, float* kbuf, int N, int C, int inner, int per_channel, int affine_per_row,
+                             int unbiased, int act, float slope, int groups, int accumulate, hipStream_t stream) {
+    gz::clear_stale_error();
+    if (!norm_shape_ok(N, C, inner)) return GZ_ERR_BAD_SHAPE;
+    const bool unfused = knobs().norm_unfused;      // experiment: the three-launch path
+    // per-channel gamma / beta over per-row statistics: their gradients are a second, tiny launch over the row sums
+    const bool channel_affine = !per_channel && !affine_per_row && (dgamma || dbeta);
+    const auto launch_channel_affine = [&] {
+        if (channel_affine)
+            hipLaunchKernelGGL(row_bwd_affine_kernel, dim3(C), dim3(64), 0, stream, (const f32x2*)workspace, dgamma,
+                               dbeta, N, C, accumulate);
+    };
+    if (!per_channel && !unfused) {
+        launch_rownorm_bwd_fused(gout, x, coef, dx, dgamma, dbeta, channel_affine ? (f32x2*)workspace : nullptr, N, C,
+                                 inner, affine_per_row, unbiased, act, slope, stream);
+        launch_channel_affine();
+        return launch_status();
+    }
+    {
+        const RowGeom rg = row_geom((long long)N * C, inner);
+        const ApplyGeom g = apply_geom(N, C, inner, per_channel, groups);
+        hipLaunchKernelGGL(norm_bwd_rowsums_kernel, dim3(row_grid(rg)), dim3(PW_THREADS), 0, stream, gout, x, coef,
+                           (f32x2*)workspace, rg, C, per_channel, g.ncoef, act, slope, g.group_rows);
+        if (per_channel && dx && !unfused) {
+            const BnFuse f = bn_fuse_geom(N, C, inner, groups);
+            hipLaunchKernelGGL(bn_bwd_apply_fused_kernel, dim3(bn_fuse_grid(f)), dim3(PW_THREADS), 0, stream, gout, x,
+                               coef, (const f32x2*)workspace, kbuf, dgamma, dbeta, dx, f, inner, act, slope, accumulate);
+            return launch_status();
+        }
+        if (per_channel) {
+            hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(C), dim3(64), 0, stream, (const f32x2*)workspace, kbuf,
+                               dgamma, dbeta, N, C, inner, groups, accumulate);
+        } else {
+            const int rows = N * C;
+            hipLaunchKernelGGL(row_bwd_finalize_kernel, dim3((rows + 255) / 256), dim3(256), 0, stream,
+                               (const f32x2*)workspace, kbuf, dgamma, dbeta, N, C, inner, affine_per_row, unbiased);
+            launch_channel_affine();
+        }
+        if (dx)
+            hipLaunchKernelGGL(norm_bwd_apply_kernel, dim3(ew_grid(g.total4)), dim3(PW_THREADS), 0, stream, gout, x,
+                               coef, kbuf, dx, g, act, slope);
+    }
+    return launch_status();
 }
 
 }  // namespace gz
@@ -1004,18 +1205,10 @@ int gz_batchnorm_stats_g(const float* x, const float* gamma, const float* beta, 
                          int inner, float eps, float momentum, int groups, hipStream_t stream) {
     gz::clear_stale_error();
     if (!norm_shape_ok(N, C, inner) || !groups_ok(N, groups)) return GZ_ERR_BAD_SHAPE;
-    RowGeom g = row_geom((long long)N * C, inner);
-    hipLaunchKernelGGL(row_sums_kernel, dim3(row_grid(g)), dim3(PW_THREADS), 0, stream, x, (f32x2*)workspace, g);
+    launch_row_sums(x, workspace, N, C, inner, stream);
     hipLaunchKernelGGL(bn_finalize_kernel<1>, dim3(C), dim3(64), 0, stream, (const f32x2*)workspace, gamma, beta, coef,
                        running_mean, running_var, num_batches_tracked, N, C, inner, eps, momentum, 0.0, groups);
     return launch_status();
-}
-
-int gz_batchnorm_stats(const float* x, const float* gamma, const float* beta, float* coef, float* running_mean,
-                       float* running_var, long long* num_batches_tracked, void* workspace, int N, int C,
-                       int inner, float eps, float momentum, hipStream_t stream) {
-    return gz_batchnorm_stats_g(x, gamma, beta, coef, running_mean, running_var, num_batches_tracked, workspace, N, C,
-                                inner, eps, momentum, 1, stream);
 }
 
 int gz_batchnorm_finalize_g(const float* partials, int rows, long long count, const float* gamma, const float* beta,
@@ -1048,8 +1241,7 @@ int gz_batchnorm_act_fwd_fused(const float* x, const float* partials, int rows, 
     double cnt = (double)count;
     if (!partials) {
         if (!workspace) return GZ_ERR_WORKSPACE;
-        RowGeom g = row_geom((long long)N * C, inner);
-        hipLaunchKernelGGL(row_sums_kernel, dim3(row_grid(g)), dim3(PW_THREADS), 0, stream, x, (f32x2*)workspace, g);
+        launch_row_sums(x, workspace, N, C, inner, stream);
         sums = (const f32x2*)workspace;
         rows = N;
         cnt = 0.0;
@@ -1057,24 +1249,16 @@ int gz_batchnorm_act_fwd_fused(const float* x, const float* partials, int rows, 
         return GZ_ERR_BAD_SHAPE;
     }
     const BnFuse f = bn_fuse_geom(N, C, inner, groups);
-    hipLaunchKernelGGL(bn_apply_fused_kernel, dim3((C / f.CB) * groups * f.S), dim3(PW_THREADS), 0, stream, x, sums, rows, cnt,
+    hipLaunchKernelGGL(bn_apply_fused_kernel, dim3(bn_fuse_grid(f)), dim3(PW_THREADS), 0, stream, x, sums, rows, cnt,
                        gamma, beta, coef, running_mean, running_var, num_batches_tracked, out, f, inner, eps, momentum,
                        act, slope);
     return launch_status();
 }
 
-int gz_batchnorm_finalize(const float* partials, int rows, long long count, const float* gamma, const float* beta,
-                          float* coef, float* running_mean, float* running_var, long long* num_batches_tracked, int C,
-                          float eps, float momentum, hipStream_t stream) {
-    return gz_batchnorm_finalize_g(partials, rows, count, gamma, beta, coef, running_mean, running_var,
-                                   num_batches_tracked, C, eps, momentum, 1, stream);
-}
-
 int gz_channel_sum(const float* x, float* out, void* workspace, int N, int C, int inner, hipStream_t stream) {
     gz::clear_stale_error();
     if (!norm_shape_ok(N, C, inner)) return GZ_ERR_BAD_SHAPE;
-    RowGeom g = row_geom((long long)N * C, inner);
-    hipLaunchKernelGGL(row_sums_kernel, dim3(row_grid(g)), dim3(PW_THREADS), 0, stream, x, (f32x2*)workspace, g);
+    launch_row_sums(x, workspace, N, C, inner, stream);
     hipLaunchKernelGGL(channel_sum_finalize_kernel, dim3(C), dim3(64), 0, stream, (const f32x2*)workspace, out, N, C);
     return launch_status();
 }
@@ -1093,8 +1277,7 @@ int gz_rownorm_stats(const float* x, const float* gamma, const float* beta, floa
     gz::clear_stale_error();
     if (!norm_shape_ok(N, C, inner)) return GZ_ERR_BAD_SHAPE;
     (void)workspace;
-    RowGeom g = row_geom((long long)N * C, inner);
-    launch_rownorm_fused(x, gamma, beta, coef, nullptr, g, C, inner, eps, affine_per_row, unbiased, ACT_NONE, 0.f, stream);
+    launch_rownorm_fused(x, gamma, beta, coef, nullptr, N, C, inner, eps, affine_per_row, unbiased, ACT_NONE, 0.f, stream);
     return launch_status();
 }
 
@@ -1103,8 +1286,7 @@ int gz_rownorm_act_fwd(const float* x, const float* gamma, const float* beta, fl
                        hipStream_t stream) {
     gz::clear_stale_error();
     if (!norm_shape_ok(N, C, inner)) return GZ_ERR_BAD_SHAPE;
-    RowGeom g = row_geom((long long)N * C, inner);
-    launch_rownorm_fused(x, gamma, beta, coef, out, g, C, inner, eps, affine_per_row, unbiased, act, slope, stream);
+    launch_rownorm_fused(x, gamma, beta, coef, out, N, C, inner, eps, affine_per_row, unbiased, act, slope, stream);
     return launch_status();
 }
 
@@ -1112,8 +1294,7 @@ int gz_rownorm_act_fwd_sigma(const float* x, const float* sigma, int groups, flo
                              int inner, float eps, int act, float slope, hipStream_t stream) {
     gz::clear_stale_error();
     if (!norm_shape_ok(N, C, inner) || !sigma || groups <= 0 || N % groups) return GZ_ERR_BAD_SHAPE;
-    RowGeom g = row_geom((long long)N * C, inner);
-    launch_rownorm_fused(x, nullptr, nullptr, coef, out, g, C, inner, eps, 0, 0, act, slope, stream, 0, sigma,
+    launch_rownorm_fused(x, nullptr, nullptr, coef, out, N, C, inner, eps, 0, 0, act, slope, stream, 0, sigma,
                          (N / groups) * C);
     return launch_status();
 }
@@ -1122,17 +1303,7 @@ int gz_rownorm_act_bwd_rows(const float* gout, const float* x, const float* coef
                             int inner, int act, float slope, hipStream_t stream) {
     gz::clear_stale_error();
     if (!norm_shape_ok(N, C, inner) || !dx || !rowsums) return GZ_ERR_BAD_SHAPE;
-    RowGeom rg = row_geom((long long)N * C, inner);
-    const int per_lane = (rg.q4 + rg.lpr - 1) / rg.lpr;
-    const int max_cache = knobs().norm_bwd_cache;
-#define GZ_RB(CACHE)                                                                                                  \
-    hipLaunchKernelGGL(rownorm_bwd_fused_kernel<CACHE>, dim3(row_grid(rg)), dim3(PW_THREADS), 0, stream, gout, x, coef, \
-                       dx, (float*)nullptr, (float*)nullptr, (f32x2*)rowsums, rg, C, inner, 0, 0, act, slope)
-    if (per_lane <= 1) GZ_RB(1);
-    else if (per_lane <= 4 && max_cache >= 4) GZ_RB(4);
-    else if (per_lane <= 16 && max_cache >= 16) GZ_RB(16);
-    else GZ_RB(0);
-#undef GZ_RB
+    launch_rownorm_bwd_fused(gout, x, coef, dx, nullptr, nullptr, (f32x2*)rowsums, N, C, inner, 0, 0, act, slope, stream);
     return launch_status();
 }
 
@@ -1140,8 +1311,7 @@ int gz_adain_const_fwd(const float* x, const float* sb, float* coef, float* out,
                        int act, float slope, hipStream_t stream) {
     gz::clear_stale_error();
     if (!norm_shape_ok(N, C, inner)) return GZ_ERR_BAD_SHAPE;
-    RowGeom g = row_geom((long long)N * C, inner);
-    launch_rownorm_fused(x, sb, sb + C, coef, out, g, C, inner, eps, 2, 1, act, slope, stream, C);
+    launch_rownorm_fused(x, sb, sb + C, coef, out, N, C, inner, eps, 2, 1, act, slope, stream, C);
     return launch_status();
 }
 
@@ -1166,22 +1336,6 @@ int gz_norm_act_fwd_g(const float* x, const float* coef, float* out, int N, int 
     return launch_status();
 }
 
-int gz_norm_act_fwd(const float* x, const float* coef, float* out, int N, int C, int inner, int per_channel,
-                    int act, float slope, hipStream_t stream) {
-    return gz_norm_act_fwd_g(x, coef, out, N, C, inner, per_channel, 1, act, slope, stream);
-}
-
-static int norm_act_bwd_impl(const float* gout, const float* x, const float* coef, float* dx, float* dgamma, float* dbeta,
-                             void* workspace, float* kbuf, int N, int C, int inner, int per_channel, int affine_per_row,
-                             int unbiased, int act, float slope, int groups, int accumulate, hipStream_t stream);
-
-int gz_norm_act_bwd(const float* gout, const float* x, const float* coef, float* dx, float* dgamma, float* dbeta,
-                    void* workspace, float* kbuf, int N, int C, int inner, int per_channel, int affine_per_row,
-                    int unbiased, int act, float slope, hipStream_t stream) {
-    return norm_act_bwd_impl(gout, x, coef, dx, dgamma, dbeta, workspace, kbuf, N, C, inner, per_channel, affine_per_row,
-                             unbiased, act, slope, 1, 0, stream);
-}
-
 /* InstanceNorm with per-channel affine (per_channel = 0, affine_per_row = 0): accumulate != 0 adds the affine gradients
  * to dgamma / dbeta (gradient sinks; first-order backward only) */
 int gz_rownorm_act_bwd_acc(const float* gout, const float* x, const float* coef, float* dx, float* dgamma, float* dbeta,
@@ -1198,57 +1352,6 @@ int gz_batchnorm_act_bwd_g(const float* gout, const float* x, const float* coef,
     if (!groups_ok(N, groups)) return GZ_ERR_BAD_SHAPE;
     return norm_act_bwd_impl(gout, x, coef, dx, dgamma, dbeta, workspace, kbuf, N, C, inner, 1, 0, 0, act, slope, groups,
                              accumulate, stream);
-}
-
-static int norm_act_bwd_impl(const float* gout, const float* x, const float* coef, float* dx, float* dgamma, float* dbeta,
-                             void* workspace, float* kbuf, int N, int C, int inner, int per_channel, int affine_per_row,
-                             int unbiased, int act, float slope, int groups, int accumulate, hipStream_t stream) {
-    gz::clear_stale_error();
-    if (!norm_shape_ok(N, C, inner)) return GZ_ERR_BAD_SHAPE;
-    RowGeom rg = row_geom((long long)N * C, inner);
-    ApplyGeom g = apply_geom(N, C, inner, per_channel, groups);
-    const bool unfused = knobs().norm_unfused;      // experiment: the three-launch path
-    if (!per_channel && !unfused) {
-        const bool channel_affine = !affine_per_row && (dgamma || dbeta);
-        const int max_cache = knobs().norm_bwd_cache;
-        const int per_lane = (rg.q4 + rg.lpr - 1) / rg.lpr;
-#define GZ_RB(CACHE)                                                                                                  \
-    hipLaunchKernelGGL(rownorm_bwd_fused_kernel<CACHE>, dim3(row_grid(rg)), dim3(PW_THREADS), 0, stream, gout, x, coef, \
-                       dx, dgamma, dbeta, channel_affine ? (f32x2*)workspace : (f32x2*)nullptr, rg, C, inner,          \
-                       affine_per_row, unbiased, act, slope)
-        if (per_lane <= 1) GZ_RB(1);
-        else if (per_lane <= 4 && max_cache >= 4) GZ_RB(4);
-        else if (per_lane <= 16 && max_cache >= 16) GZ_RB(16);
-        else GZ_RB(0);
-#undef GZ_RB
-        if (channel_affine)
-            hipLaunchKernelGGL(row_bwd_affine_kernel, dim3(C), dim3(64), 0, stream, (const f32x2*)workspace, dgamma,
-                               dbeta, N, C, accumulate);
-        return launch_status();
-    }
-    hipLaunchKernelGGL(norm_bwd_rowsums_kernel, dim3(row_grid(rg)), dim3(PW_THREADS), 0, stream, gout, x, coef,
-                       (f32x2*)workspace, rg, C, per_channel, g.ncoef, act, slope, g.group_rows);
-    if (per_channel && dx && !unfused) {
-        const BnFuse f = bn_fuse_geom(N, C, inner, groups);
-        hipLaunchKernelGGL(bn_bwd_apply_fused_kernel, dim3((C / f.CB) * groups * f.S), dim3(PW_THREADS), 0, stream, gout, x, coef,
-                           (const f32x2*)workspace, kbuf, dgamma, dbeta, dx, f, inner, act, slope, accumulate);
-        return launch_status();
-    }
-    if (per_channel) {
-        hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(C), dim3(64), 0, stream, (const f32x2*)workspace, kbuf, dgamma,
-                           dbeta, N, C, inner, groups, accumulate);
-    } else {
-        int rows = N * C;
-        hipLaunchKernelGGL(row_bwd_finalize_kernel, dim3((rows + 255) / 256), dim3(256), 0, stream,
-                           (const f32x2*)workspace, kbuf, dgamma, dbeta, N, C, inner, affine_per_row, unbiased);
-        if (!affine_per_row && (dgamma || dbeta))
-            hipLaunchKernelGGL(row_bwd_affine_kernel, dim3(C), dim3(64), 0, stream, (const f32x2*)workspace, dgamma,
-                               dbeta, N, C, accumulate);
-    }
-    if (dx)
-        hipLaunchKernelGGL(norm_bwd_apply_kernel, dim3(ew_grid(g.total4)), dim3(PW_THREADS), 0, stream, gout, x, coef,
-                           kbuf, dx, g, act, slope);
-    return launch_status();
 }
 
 int gz_rownorm_act_bwd2(const float* gout, const float* v, const float* x, const float* coef, float* gg_out,
@@ -1284,6 +1387,33 @@ int gz_tanh_bwd2(const float* v, const float* g, const float* out, float* res, l
     hipLaunchKernelGGL(tanh_bwd2_kernel, dim3(ew_grid(count / 4)), dim3(PW_THREADS), 0, stream, v, g, out, res,
                        count / 4);
     return launch_status();
+}
+
+/* the entry points from before statistics groups: one group, nothing accumulated */
+int gz_batchnorm_stats(const float* x, const float* gamma, const float* beta, float* coef, float* running_mean,
+                       float* running_var, long long* num_batches_tracked, void* workspace, int N, int C,
+                       int inner, float eps, float momentum, hipStream_t stream) {
+    return gz_batchnorm_stats_g(x, gamma, beta, coef, running_mean, running_var, num_batches_tracked, workspace, N, C,
+                                inner, eps, momentum, 1, stream);
+}
+
+int gz_batchnorm_finalize(const float* partials, int rows, long long count, const float* gamma, const float* beta,
+                          float* coef, float* running_mean, float* running_var, long long* num_batches_tracked, int C,
+                          float eps, float momentum, hipStream_t stream) {
+    return gz_batchnorm_finalize_g(partials, rows, count, gamma, beta, coef, running_mean, running_var,
+                                   num_batches_tracked, C, eps, momentum, 1, stream);
+}
+
+int gz_norm_act_fwd(const float* x, const float* coef, float* out, int N, int C, int inner, int per_channel,
+                    int act, float slope, hipStream_t stream) {
+    return gz_norm_act_fwd_g(x, coef, out, N, C, inner, per_channel, 1, act, slope, stream);
+}
+
+int gz_norm_act_bwd(const float* gout, const float* x, const float* coef, float* dx, float* dgamma, float* dbeta,
+                    void* workspace, float* kbuf, int N, int C, int inner, int per_channel, int affine_per_row,
+                    int unbiased, int act, float slope, hipStream_t stream) {
+    return norm_act_bwd_impl(gout, x, coef, dx, dgamma, dbeta, workspace, kbuf, N, C, inner, per_channel, affine_per_row,
+                             unbiased, act, slope, 1, 0, stream);
 }
 
 }  // extern "C"

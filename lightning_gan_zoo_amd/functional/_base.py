@@ -284,7 +284,10 @@ def _conv_fwd_raw(x, w, bias, geom, act, slope):
 
 
 _NO_BN_FUSE = bool(os.environ.get("GZ_NO_BN_FUSE"))      # experiment: statistics by a separate pass, as in round 1
-_NORM_UNFUSED = bool(os.environ.get("GZ_BN_FINALIZE_LAUNCH"))    # experiment: the separate bn_finalize launch (round 4)
+# experiment: the separate bn_finalize launch (round 4); like the switches of csrc/gz_knobs.h it is honoured only in a
+# process started with GZ_EXPERIMENTS=1
+_NORM_UNFUSED = (os.environ.get("GZ_EXPERIMENTS", "0")[:1] not in ("", "0")       # (the gate as gz_knobs.h reads it)
+                 and bool(os.environ.get("GZ_BN_FINALIZE_LAUNCH")))
 
 
 def _conv_fwd_stats_raw(x, w, geom):
