@@ -1,5 +1,6 @@
 // Part of the fp32 implicit-GEMM core (see gz_igemm.h): the igemm2 skeleton of rounds 3-5 (one wavefront per SIMD, LDS-DMA
-// ring of three stages, hand-ordered k-step; igemm2_kernel / igemm2w_kernel / igemm2r_kernel, their loaders and launchers).
+// ring of three stages -- igemm2_kernel: of igemm2_depth() stages, a compile-time property of the instantiation --,
+// hand-ordered k-step; igemm2_kernel / igemm2w_kernel / igemm2r_kernel, their loaders and launchers).
 #pragma once
 #include "gz_igemm_core.h"
 
@@ -13,9 +14,16 @@ namespace gz {
 // of them stalls at a barrier every 32 MFMAs.  Here ONE wavefront per SIMD owns a 128 x 128 (or 128 x 64) accumulator
 // tile -- a 256 x 256 / 256 x 128 workgroup tile -- and runs an in-order, software-pipelined stream in which the
 // MFMAs issue back to back and everything else sits in their shadow:
-//   * operands arrive by LDS-DMA into a THREE-deep ring of stages; the pieces of chunk t+2 are issued one per k-step
-//     between the MFMAs of chunk t, waited for with a COUNTED s_waitcnt vmcnt(N) (never 0 inside the loop) and made
-//     visible by ONE raw s_barrier per chunk (128 MFMAs per wavefront) -- __syncthreads() would drain the DMA queue;
+//   * operands arrive by LDS-DMA into a ring of D stages (D = 3 unless igemm2_depth() says otherwise); the pieces of
+//     chunk t+D-1 are issued one per k-step between the MFMAs of chunk t, waited for with a COUNTED s_waitcnt
+//     vmcnt((D-2) * pieces per chunk) (not 0 inside the loop at D >= 3: a chunk's pieces stay in flight across the
+//     barrier) and made visible by ONE raw s_barrier per chunk (128 MFMAs per wavefront at TN = 4, 32 at TN = 1) --
+//     __syncthreads() would drain the DMA queue.  Where igemm2_interval() is 2: one wait + barrier per TWO chunks, the
+//     ring handled in P pairs of stages, the wait vmcnt((P-2) * 2 * pieces per chunk).  With P = 2 (TN = 1, KG = 1:
+//     four stages, three workgroups per CU) that IS vmcnt(0) in the loop -- a double buffer of pairs: the next pair's
+//     pieces go out in k-steps 0-5 of the pair's 16 and have ten k-steps (2560 cycles of the wavefront's own MFMAs) to
+//     land, nothing stays in flight across the barrier.  A loader with more pieces per chunk (PPS > 1, or NP near
+//     STEPS) issues later into the pair and should not be given P = 2 without measuring its wait;
 //   * the wait + barrier sit inside the LAST k-step of a chunk, in front of its MFMAs, so the first fragments of the
 //     next chunk are fetched under those MFMAs;
 //   * fragments are double-buffered in registers one k-step ahead (8 ds_read_b32 per 16 MFMAs).
@@ -27,7 +35,37 @@ namespace gz {
 //   void init(const Params&, int tile, int y, int tid);
 //   void issue_piece(int kc, float* stage_base, int p, bool live);   // p in [0, PIECES), wave-uniform control flow
 // =====================================================================================================================
-constexpr int STAGES2 = 3;
+constexpr int STAGES2 = 3;      // igemm2w_kernel's ring, and the default depth of igemm2_kernel's (igemm2_depth below)
+// Ring depth of igemm2_kernel per instantiation.  The three stages were sized for the 128 x 128 wave tile: 128 MFMAs
+// = 8192 cycles per chunk, a prefetch distance of two chunks.  The 128 x 32 wave tile (TN = 1) has 2048 cycles per
+// chunk.  Depth D (barrier interval 1): the prologue issues chunks 0 .. D-2 and waits for chunk 0, chunk t+D-1 is issued
+// during chunk t into the stage chunk t-1 was read from, and the counted wait of chunk t leaves (D-2) * NP pieces in
+// flight.  The candidates are compared with -D builds of the library.  Measured: at three stages the
+// counted wait never waits, depth 4 and 5 change nothing; what the TN = 1 loop loses it loses at the barrier, so what
+// ships for TN = 1 is the barrier interval below with the stages it needs (6 = three pairs, or 4 = two pairs where
+// three workgroups share the CU's LDS), and TN = 2 keeps 3 / 1.
+// tests/test_igemm2_ring_gpu.py reads the four TN1 #defines below and sizes its cases around them.
+#ifndef GZ2_DEPTH_TN1_KG2
+#define GZ2_DEPTH_TN1_KG2 6
+#endif
+#ifndef GZ2_DEPTH_TN1_KG1
+#define GZ2_DEPTH_TN1_KG1 4
+#endif
+#ifndef GZ2_DEPTH_TN2_KG2
+#define GZ2_DEPTH_TN2_KG2 3
+#endif
+#ifndef GZ2_DEPTH_TN2_KG1
+#define GZ2_DEPTH_TN2_KG1 3
+#endif
+// Barrier interval of the same instantiations: chunks per counted wait + s_barrier.  With interval 2 the ring is handled
+// in PAIRS of stages -- the loop body is two chunks (16 k-steps, 64 MFMAs per wavefront at TN = 1: what the skeleton was
+// sized for), the depth counts pairs' stages (a multiple of 2), the pieces of pair p+P-1 are issued during pair p.
+#ifndef GZ2_BARRIER_TN1_KG2
+#define GZ2_BARRIER_TN1_KG2 2
+#endif
+#ifndef GZ2_BARRIER_TN1_KG1
+#define GZ2_BARRIER_TN1_KG1 2
+#endif
 constexpr uint32_t SOFF_OOB = 0x80000000u;      // scalar offset that puts every lane of a buffer access out of range
 
 template <int WM_, int WN_, int TN_, int OCC_, int TM_ = 4>
@@ -540,10 +578,50 @@ constexpr int step_brow_of(int m, int S) {         // first row of the B image k
 // accumulators, group 0 adds them and runs the epilogue).  For launches whose tiles x reduction splits give a CU only
 // one workgroup: the CU then still holds two wavefronts per SIMD -- the second one is what hides the non-MFMA
 // instructions of the k-step -- without the slabs + finish pass that a global split of the reduction costs.
+// Stages of the LDS-DMA ring (see GZ2_DEPTH_* above): deeper than three only for the 16-byte row loaders of the k4 s2 p1
+// layers on 256-row tiles (8 LDS rows per A image: a stage is 12-17 KB), where the LDS is there -- the gathers' stages
+// are 20 KB and more and keep three.
+constexpr size_t LDS_PER_CU = 160 * 1024;
+template <class AL, class BL>
+constexpr int igemm2_stage_floats() { return AL::ROWS * AL::LD + igemm2_a_extra<AL>() + BL::ROWS * BL::LD; }
+// LDS of a workgroup whose ring(s) have `depth` stages (KG = 2: two rings, or the parked accumulators if those are larger)
+template <class Cfg, class AL, class BL, int KG>
+constexpr size_t igemm2_lds_bytes_at(int depth) {
+    if (KG == 1) return (size_t)(depth * igemm2_stage_floats<AL, BL>() + 32) * 4;
+    const size_t rings = (size_t)(2 * ((depth * igemm2_stage_floats<AL, BL>() + 63) / 64 * 64) + 32) * 4;
+    const size_t park = (size_t)Cfg::TM * Cfg::TN * 16 * NT * 4;
+    return rings > park ? rings : park;
+}
+// The instantiations GZ2_DEPTH_* / GZ2_BARRIER_* speak of.  One exception, explicit: ConvFwdA2 with 64 output columns
+// per row (its zeroed region is 388 floats per stage) fits neither six stages in two rings nor four stages three times
+// into a CU's LDS and keeps 3 / 1.  Nothing else is lowered behind a -D build's back: igemm2_kernel asserts that what
+// these return fits.
+template <class Cfg, class AL, class BL, int KG>
+constexpr bool igemm2_tunable() {
+    return Cfg::BM == 256 && (is_rowshare<AL>::value || is_fwdrows<AL>::value) && !is_dualmode<AL>::value &&
+           fwd_ow<AL>() < 64;
+}
+template <class Cfg, class AL, class BL, int KG>
+constexpr int igemm2_interval() {      // chunks per counted wait + barrier
+    if (igemm2_tunable<Cfg, AL, BL, KG>() && Cfg::TN == 1) return KG == 2 ? GZ2_BARRIER_TN1_KG2 : GZ2_BARRIER_TN1_KG1;
+    return 1;
+}
+template <class Cfg, class AL, class BL, int KG>
+constexpr int igemm2_depth() {         // stages of the ring (a multiple of the interval)
+    if (igemm2_tunable<Cfg, AL, BL, KG>()) {
+        if (Cfg::TN == 1) return KG == 2 ? GZ2_DEPTH_TN1_KG2 : GZ2_DEPTH_TN1_KG1;
+        if (Cfg::TN == 2) return KG == 2 ? GZ2_DEPTH_TN2_KG2 : GZ2_DEPTH_TN2_KG1;
+    }
+    return STAGES2;
+}
 template <class Cfg, class AL, class BL, int KG>
 constexpr int igemm2_ring_floats() {
-    return ((STAGES2 * (AL::ROWS * AL::LD + igemm2_a_extra<AL>() + BL::ROWS * BL::LD) + 63) / 64) * 64;
+    return ((igemm2_depth<Cfg, AL, BL, KG>() * igemm2_stage_floats<AL, BL>() + 63) / 64) * 64;
 }
+template <class Cfg, class AL, class BL>
+constexpr size_t igemm2_lds_bytes() { return igemm2_lds_bytes_at<Cfg, AL, BL, 1>(igemm2_depth<Cfg, AL, BL, 1>()); }
+template <class Cfg, class AL, class BL>
+constexpr size_t igemm2_lds_bytes_kg2() { return igemm2_lds_bytes_at<Cfg, AL, BL, 2>(igemm2_depth<Cfg, AL, BL, 2>()); }
 
 template <class Cfg, class AL, class BL, class Epi, int KG = 1>
 __global__ __launch_bounds__(NT * KG, KG == 1 ? Cfg::OCC : 2) void igemm2_kernel(typename AL::Params pa, typename BL::Params pb,
@@ -563,6 +641,15 @@ __global__ __launch_bounds__(NT * KG, KG == 1 ? Cfg::OCC : 2) void igemm2_kernel
     constexpr int A_ELEMS = AL::ROWS * LDA + A_EXTRA, B_ELEMS = BL::ROWS * LDB;
     constexpr int STAGE = A_ELEMS + B_ELEMS;
     constexpr int PAD = 16;
+    constexpr int DEPTH = igemm2_depth<Cfg, AL, BL, KG>();      // stages of the ring
+    constexpr int BI = igemm2_interval<Cfg, AL, BL, KG>();      // chunks per barrier: the loop body is a GROUP of BI chunks
+    constexpr int GROUPS = DEPTH / BI;                          // ... and the ring holds this many groups of stages
+    static_assert(DEPTH % BI == 0 && (BI == 1 ? GROUPS >= 3 : GROUPS >= 2) && (BI == 1 || (BI == 2 && !DM)),
+                  "group t+GROUPS-1 lands in the stages group t-1 was read from");
+    // a deeper ring must not cost a resident workgroup (the gathers' three-stage forms are throttled by their LDS already)
+    static_assert(DEPTH == STAGES2 || (KG == 2 ? igemm2_lds_bytes_kg2<Cfg, AL, BL>()
+                                               : Cfg::OCC * igemm2_lds_bytes<Cfg, AL, BL>()) <= LDS_PER_CU,
+                  "workgroups per CU x LDS per workgroup");
     extern __shared__ __attribute__((aligned(16))) float smem2[];
     const int kg = KG == 1 ? 0 : __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 8);      // wave group
     float* const ring = smem2 + PAD + kg * igemm2_ring_floats<Cfg, AL, BL, KG>();   // stage i: [B image][A image]
@@ -645,7 +732,8 @@ __global__ __launch_bounds__(NT * KG, KG == 1 ? Cfg::OCC : 2) void igemm2_kernel
             a_addr[i] = zero ? lds0 + (uint32_t)(B_ELEMS + AL::ZERO_COL) * 4u : a_addr[i] + (uint32_t)(sh * 4);
         }
         // the pad columns of every row of every stage
-        if (tid < STAGES2 * AL::ROWS * 4) {
+        static_assert(DEPTH * AL::ROWS * 4 <= NT, "one pad float per thread");
+        if (tid < DEPTH * AL::ROWS * 4) {
             const int st = tid / (AL::ROWS * 4), q = tid % (AL::ROWS * 4);
             ring[st * STAGE + B_ELEMS + (q >> 2) * LDA + AL::ZERO_COL + (q & 3)] = 0.f;
         }
@@ -667,21 +755,24 @@ __global__ __launch_bounds__(NT * KG, KG == 1 ? Cfg::OCC : 2) void igemm2_kernel
             a_addr[i] = lds0 + (uint32_t)(B_ELEMS + e) * 4u;
             a_odd[i] = lds0 + (uint32_t)(B_ELEMS + o) * 4u;
         }
-        for (int q = tid; q < STAGES2 * A_EXTRA; q += NT)
+        for (int q = tid; q < DEPTH * A_EXTRA; q += NT)
             ring[(q / A_EXTRA) * STAGE + B_ELEMS + AL::ZERO + q % A_EXTRA] = 0.f;
     }
     const uint32_t b_addr = lds0 + (uint32_t)(half * LDB + wn * TN * 32 + l32) * 4u;
 
     constexpr int NPA = AL::PIECES, NPB = BL::PIECES, NP = NPA + NPB, STEPS = ksteps_of<AL>();
-    static_assert(STEPS == 8 || STEPS == 12, "k-steps per chunk");
+    static_assert((STEPS == 8 || STEPS == 12) && (BI == 1 || STEPS == 8), "k-steps per chunk, per group 8, 12 or 16");
     constexpr int PPS = (NP + STEPS - 1) / STEPS;          // LDS-DMA pieces per k-step (1 for the 16-byte loaders)
-    static_assert(PPS <= 4 && NP < 64, "pieces are spread over the k-step's four MFMA rows; vmcnt is 6 bits");
+    static_assert(PPS <= 4 && (DEPTH - BI) * NP < 64,
+                  "pieces are spread over the k-step's four MFMA rows; vmcnt is 6 bits and DEPTH-BI chunks are in flight");
+    constexpr int NWAIT = (DEPTH - 2 * BI) * NP;           // in flight behind the group that the counted wait is for
+    constexpr int GSTEPS = BI * STEPS;                     // k-steps of the loop body
     auto issue_piece = [&](int kc, int st, int p, bool live) {
 #ifdef GZ2_EXP_NODMA       // timing experiments only (wrong results)
-        if (kc >= kc0 + 2) return;
+        if (kc >= kc0 + DEPTH - BI) return;
 #endif
 #ifdef GZ2_EXP_SAMECHUNK
-        if (kc >= kc0 + 2) kc = kc0;
+        if (kc >= kc0 + DEPTH - BI) kc = kc0;
 #endif
         float* sb = ring + st * STAGE;
         if (p < NPA) al.issue_piece(kc, sb + B_ELEMS, p, live);
@@ -708,14 +799,16 @@ __global__ __launch_bounds__(NT * KG, KG == 1 ? Cfg::OCC : 2) void igemm2_kernel
         }
     };
     auto fetch = [&](auto Sc, uint32_t so, float (&af)[TM], float (&bf)[TN]) {
-        constexpr int S = decltype(Sc)::value;
-        constexpr int AO = (RS ? LDA : 2 * LDA) * S * 4, BO = 2 * S * LDB * 4;
+        // (k-step Sc of the GROUP: chunk JO / (STAGE * 4) of it, that chunk's k-step S)
+        constexpr int S = decltype(Sc)::value % STEPS, JO = decltype(Sc)::value / STEPS * STAGE * 4;
+        constexpr int AO = (RS ? LDA : 2 * LDA) * S * 4 + JO, BO = 2 * S * LDB * 4 + JO;
+        static_assert(AO + 2 * LDA * 4 < 65536 && BO + 512 < 65536, "ds_read immediate offsets");
 #ifdef GZ2_EXP_NOFETCH
         if (so != 0xFFFFFFFFu) return;
 #endif
         // immediate offsets only: no VALU address arithmetic inside the loop (`a_addr[i] + so` is per-chunk)
         if constexpr (FR) {
-            constexpr int FO = (S >> 1) * 2 * fwd_ow<AL>() * 4;
+            constexpr int FO = (S >> 1) * 2 * fwd_ow<AL>() * 4 + JO;
             af[0] = lds_rd<FO>(((S & 1) ? a_odd[0] : a_addr[0]) + so);
             af[1] = lds_rd<FO>(((S & 1) ? a_odd[1] : a_addr[1]) + so);
             af[2] = lds_rd<FO>(((S & 1) ? a_odd[2] : a_addr[2]) + so);
@@ -738,16 +831,18 @@ __global__ __launch_bounds__(NT * KG, KG == 1 ? Cfg::OCC : 2) void igemm2_kernel
     auto mask = [&](float (&)[TM]) {};      // (row-shared images: the zero column replaces the register masks)
 
     if (kcA < kcB) {
+        // chunks 0 .. DEPTH-BI-1 into the stages of those numbers; the first group has landed when all but the others'
+        // pieces have
 #pragma unroll
-        for (int p = 0; p < NP; ++p) issue_piece(kc0, 0, p, kc0 < kc1);
+        for (int d = 0; d < DEPTH - BI; ++d)
 #pragma unroll
-        for (int p = 0; p < NP; ++p) issue_piece(kc0 + 1, 1, p, kc0 + 1 < kc1);
+            for (int p = 0; p < NP; ++p) issue_piece(kc0 + d, d, p, kc0 + d < kc1);
         // lgkmcnt(0) as well: the zeroed pad columns / A_EXTRA region above were plain ds_writes, and gfx950's back-off
         // barrier does not wait for a wavefront's outstanding LDS operations by itself
 #ifdef GZ2_EXP_NO_LGKM_PROLOGUE
-        asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NP) : "memory");
+        asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NWAIT) : "memory");
 #else
-        asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(NP) : "memory");
+        asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(NWAIT) : "memory");
 #endif
         __builtin_amdgcn_s_barrier();
 #ifdef GZ2_STAMPS
@@ -755,7 +850,8 @@ __global__ __launch_bounds__(NT * KG, KG == 1 ? Cfg::OCC : 2) void igemm2_kernel
 #endif
         float af[2][TM], bf[2][TN];
 #ifdef GZ2_STEP_STAMPS
-        unsigned long long step_cyc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, step_t = __builtin_amdgcn_s_memtime();
+        unsigned long long step_cyc[STEPS] = {}, step_t = __builtin_amdgcn_s_memtime();     // (the first 8 are reported)
+        unsigned long long wait_cyc[2] = {0, 0};      // inside the last k-step: the counted vmcnt wait, the s_barrier
 #endif
         if constexpr (DM) {
 #pragma unroll
@@ -772,11 +868,13 @@ __global__ __launch_bounds__(NT * KG, KG == 1 ? Cfg::OCC : 2) void igemm2_kernel
         // (dual mode: the row-shared chunks and the plain chunks are TWO loops, one after the other -- a per-chunk branch
         // between the two k-step forms inside one loop made the register allocator spill accumulators in every iteration)
         auto run_chunks = [&](int k_from, int k_to, auto Mc) {
-        for (int kc = k_from; kc < k_to; ++kc) {
-            int s1 = stage + 1; if (s1 >= STAGES2) s1 -= STAGES2;
-            int s2 = s1 + 1; if (s2 >= STAGES2) s2 -= STAGES2;
-            const uint32_t so = (uint32_t)(stage * STAGE * 4), sno = (uint32_t)(s1 * STAGE * 4);
-            const bool more = kc + 2 < kc1;
+        // (`stage` counts GROUPS of BI stages; a last group that is not full runs its missing chunks as zeros, like the
+        // chunks past kc1 of a wave group)
+        for (int kc = k_from; kc < k_to; kc += BI) {
+            int s1 = stage + 1; if (s1 >= GROUPS) s1 -= GROUPS;
+            int s2 = stage - 1; if (s2 < 0) s2 += GROUPS;         // the stages group kc-BI was read from: group kc+DEPTH-BI's
+            const uint32_t so = (uint32_t)(stage * BI * STAGE * 4), sno = (uint32_t)(s1 * BI * STAGE * 4);
+            const bool more = kc + DEPTH - BI < kc1, more1 = kc + DEPTH - BI + 1 < kc1;
             auto kstep = [&](auto Sc) {
                 constexpr int S = decltype(Sc)::value;
                 constexpr int MD = decltype(Mc)::value;          // multi-mode loaders: this loop's k-step form
@@ -797,16 +895,17 @@ __global__ __launch_bounds__(NT * KG, KG == 1 ? Cfg::OCC : 2) void igemm2_kernel
                     if constexpr (DM) fetch_m(S2c, Mc, o, fa, fb);
                     else fetch(S2c, o, fa, fb);
                 };
-                // chunk kc+2's pieces go out in the FIRST k-steps, PPS per step, one behind each MFMA row (the stage
-                // they overwrite was last read in chunk kc-1, behind its barrier), so that by the last k-step exactly
-                // NP are in flight
+                // the pieces of group kc+DEPTH-BI go out in the FIRST k-steps, PPS per step, one behind each MFMA row
+                // (the stages they overwrite were last read in group kc-BI, behind its barrier), so that by the last
+                // k-step exactly (DEPTH-BI) * NP are in flight: group kc+BI's, the oldest, and NWAIT behind them
                 auto pieces = [&](auto Rowc) {        // behind MFMA row `Rowc` (a single piece per k-step: behind row 1)
                     constexpr int row = decltype(Rowc)::value;
                     constexpr int r = PPS == 1 ? (row == 1 ? 0 : -1) : row;
                     constexpr int q = S * PPS + r;
-                    if constexpr (r >= 0 && r < PPS && q < NP) issue_piece(kc + 2, s2, q, more);
+                    if constexpr (r >= 0 && r < PPS && q < BI * NP)
+                        issue_piece(kc + DEPTH - BI + q / NP, s2 * BI + q / NP, q % NP, q / NP == 0 ? more : more1);
                 };
-                if constexpr (S + 1 < STEPS) {
+                if constexpr (S + 1 < GSTEPS) {
                     fetch_same(std::integral_constant<int, S + 1>{}, so, af[n], bf[n]);
                     mfma_row(acc[0], af[c][0], bf[c]);
                     pieces(std::integral_constant<int, 0>{});
@@ -817,22 +916,35 @@ __global__ __launch_bounds__(NT * KG, KG == 1 ? Cfg::OCC : 2) void igemm2_kernel
                     if constexpr (TM == 4) mfma_row(acc[3], af[c][3], bf[c]);
                     pieces(std::integral_constant<int, 3>{});
                 } else {
-                    // last k-step: half of its MFMAs, then chunk kc+1 must have landed (all but the NP pieces of chunk
-                    // kc+2) and every wavefront must be done with this stage's fragments; the first fragments of
-                    // chunk kc+1 are fetched under the other half
+                    // last k-step: half of its MFMAs, then group kc+BI must have landed (all but the NWAIT pieces of
+                    // the groups behind it) and every wavefront must be done with this group's fragments; the first
+                    // fragments of chunk kc+BI are fetched under the other half
                     mfma_row(acc[0], af[c][0], bf[c]);
                     pieces(std::integral_constant<int, 0>{});
                     if constexpr (TM == 4) mfma_row(acc[1], af[c][1], bf[c]);
                     pieces(std::integral_constant<int, 1>{});
                     pieces(std::integral_constant<int, 2>{});
                     pieces(std::integral_constant<int, 3>{});
+#ifdef GZ2_STEP_STAMPS      // diagnostic: the counted wait (the DMA) and the barrier (the other wavefronts) apart
+                    const unsigned long long tw0 = __builtin_amdgcn_s_memtime();
+#endif
 #ifndef GZ2_EXP_NOVMWAIT
-                    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NP) : "memory");
+                    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NWAIT) : "memory");
+#endif
+#ifdef GZ2_STEP_STAMPS
+                    const unsigned long long tw1 = __builtin_amdgcn_s_memtime();
 #endif
 #ifndef GZ2_EXP_NOBARRIER
                     __builtin_amdgcn_s_barrier();
 #endif
-                    if constexpr (DM) fetch_first(kc + 1, sno, af[n], bf[n]);      // the next chunk's, in ITS mode
+#ifdef GZ2_STEP_STAMPS
+                    {
+                        const unsigned long long tw2 = __builtin_amdgcn_s_memtime();
+                        wait_cyc[0] += tw1 - tw0;
+                        wait_cyc[1] += tw2 - tw1;
+                    }
+#endif
+                    if constexpr (DM) fetch_first(kc + BI, sno, af[n], bf[n]);     // the next chunk's, in ITS mode
                     else fetch(std::integral_constant<int, 0>{}, sno, af[n], bf[n]);
                     if constexpr (TM == 4) {
                         mfma_row(acc[2], af[c][2], bf[c]);
@@ -844,7 +956,7 @@ __global__ __launch_bounds__(NT * KG, KG == 1 ? Cfg::OCC : 2) void igemm2_kernel
 #ifdef GZ2_STEP_STAMPS      // diagnostic: cycles per k-step position, summed over the chunks
                 {
                     const unsigned long long t = __builtin_amdgcn_s_memtime();
-                    step_cyc[S] += t - step_t;
+                    step_cyc[S % STEPS] += t - step_t;
                     step_t = t;
                 }
 #endif
@@ -859,11 +971,17 @@ __global__ __launch_bounds__(NT * KG, KG == 1 ? Cfg::OCC : 2) void igemm2_kernel
             kstep(std::integral_constant<int, 5>{});
             kstep(std::integral_constant<int, 6>{});
             kstep(std::integral_constant<int, 7>{});
-            if constexpr (STEPS == 12) {
+            if constexpr (GSTEPS >= 12) {
                 kstep(std::integral_constant<int, 8>{});
                 kstep(std::integral_constant<int, 9>{});
                 kstep(std::integral_constant<int, 10>{});
                 kstep(std::integral_constant<int, 11>{});
+            }
+            if constexpr (GSTEPS == 16) {
+                kstep(std::integral_constant<int, 12>{});
+                kstep(std::integral_constant<int, 13>{});
+                kstep(std::integral_constant<int, 14>{});
+                kstep(std::integral_constant<int, 15>{});
             }
             stage = s1;
         }
@@ -883,6 +1001,13 @@ __global__ __launch_bounds__(NT * KG, KG == 1 ? Cfg::OCC : 2) void igemm2_kernel
 #ifdef GZ2_STEP_STAMPS
         if (tid == 0 && blockIdx.x < 64)
             for (int q = 0; q < 8; ++q) gz2_stamps[(size_t)(8192 - 64 + blockIdx.x) * 8 + q] = step_cyc[q];
+        // (rows 8192-128 .. 8192-1 are the main per-workgroup rows of a grid above 8064 workgroups too, and every z-slab
+        // with blockIdx.x < 64 writes them: the last writer stays -- fine for a diagnostic of grids of a few hundred)
+        if (tid == 0 && kg == 0 && blockIdx.x < 64) {
+            gz2_stamps[(size_t)(8192 - 128 + blockIdx.x) * 8 + 0] = wait_cyc[0];
+            gz2_stamps[(size_t)(8192 - 128 + blockIdx.x) * 8 + 1] = wait_cyc[1];
+            gz2_stamps[(size_t)(8192 - 128 + blockIdx.x) * 8 + 2] = (unsigned long long)(kend - kc0);
+        }
 #endif
     }
 
@@ -1444,17 +1569,6 @@ inline int launch_igemm2r(const typename AL::Params& pa, const typename BL::Para
     }
     hipLaunchKernelGGL(kern, grid, dim3(NT), lds, stream, pa, pb, pe, gm);
     return launch_status();
-}
-
-template <class Cfg, class AL, class BL>
-constexpr size_t igemm2_lds_bytes() {
-    return (size_t)(STAGES2 * (AL::ROWS * AL::LD + igemm2_a_extra<AL>() + BL::ROWS * BL::LD) + 32) * 4;
-}
-template <class Cfg, class AL, class BL>
-constexpr size_t igemm2_lds_bytes_kg2() {
-    const size_t rings = (size_t)(2 * igemm2_ring_floats<Cfg, AL, BL, 2>() + 32) * 4;
-    const size_t park = (size_t)Cfg::TM * Cfg::TN * 16 * NT * 4;
-    return rings > park ? rings : park;
 }
 
 // Which launches run two wave groups per workgroup (igemm2_kernel<.., KG = 2>): the k4 s2 p1 loaders of the DCGAN

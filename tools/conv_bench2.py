@@ -2,11 +2,18 @@
 ~1.9 to ~2.39 GHz over the first ~40 ms of load (tools/igemm2_probe.hip, in-kernel s_memtime / s_memrealtime), so
 every measurement is preceded by 0.3 s of the same launches and nothing synchronises in between.
 
-    python tools/conv_bench2.py [bs] [ops: f,d,w] [--stats]
+    python tools/conv_bench2.py [bs] [ops: f,d,w] [--stats] [--stamps] [--sha1]
+
+--stamps (a library built with -DGZ2_STAMPS, GZ_LIB=...): per-workgroup prologue / loop / epilogue cycles of the last
+launch; with -DGZ2_STEP_STAMPS also the cycles wavefront 0 of workgroups 0-63 spent at the counted vmcnt wait and at the
+s_barrier of a chunk group's last k-step ("Ring depth and barrier interval").  --sha1 prints a digest of
+each result (seeded inputs), to compare two builds bit for bit; run one process per library and alternate them.
 """
 import os
 import sys
 import time
+
+import hashlib
 
 import torch
 
@@ -14,6 +21,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from lightning_gan_zoo_amd import functional as F      # noqa: E402
 
 g = F.K4S2P1
+torch.manual_seed(1234)
 bs = int(sys.argv[1]) if len(sys.argv) > 1 else 512
 ops = sys.argv[2].split(",") if len(sys.argv) > 2 else ["f", "d", "w"]
 stats = "--stats" in sys.argv
@@ -58,16 +66,31 @@ for name, C, H, K in layers:
             lab = ""
         t = timeit(fn)
         out += ' %s %7.3f ms %6.1f TF |' % (op, t, fl / t / 1e9)
+        if "--sha1" in sys.argv:
+            res = fn()
+            h = hashlib.sha1()
+            for r in (res if isinstance(res, (tuple, list)) else (res,)):
+                if torch.is_tensor(r):
+                    h.update(r.detach().cpu().numpy().tobytes())
+            out += ' sha1 %s |' % h.hexdigest()[:10]
         if "--stamps" in sys.argv:
             import ctypes
             import numpy as np
             from lightning_gan_zoo_amd._lib import lib
             dll = lib.load()
             if hasattr(dll, "gz_debug_read_stamps"):
-                nwg = 2048
+                nwg = 8192
                 buf = np.zeros((nwg, 8), dtype=np.uint64)
                 dll.gz_debug_read_stamps(ctypes.c_void_p(buf.ctypes.data), nwg)
-                b = buf[buf[:, 3] > 0].astype(np.float64)
+                b = buf[:nwg - 128]
+                b = b[b[:, 3] > 0].astype(np.float64)
+                if len(b):      # rows of the last launch only (the buffer keeps what earlier, larger grids wrote)
+                    b = b[b[:, 4] >= b[:, 4].max() - 60000]
+                w = buf[nwg - 128:nwg - 64].astype(np.float64)
+                w = w[w[:, 2] > 0]
+                if len(w):      # GZ2_STEP_STAMPS: [cycles at the counted wait, at the barrier, chunks of the loop]
+                    out += ' [loop of %.0f chunks: %.0f cyc at the counted wait, %.0f at the barrier]' % (
+                        w[:, 2].mean(), w[:, 0].mean(), w[:, 1].mean())
                 if len(b):
                     ideal = b[:, 6] * 8 * b[:, 7] * 64
                     clk = (b[:, 3] - b[:, 0]) / (b[:, 5] - b[:, 4]) * 100
