@@ -609,6 +609,33 @@ int gz_sqrtm_product_pair(const double* a0, const double* b0, double* c0, double
 size_t gz_sqrtm_trace_norm_workspace_bytes(int d);
 int gz_sqrtm_trace_norm(const double* a, int d, double* out, void* workspace, size_t ws_bytes, hipStream_t stream);
 
+/* ---- Inception Score on the device (csrc/gz_inception_score.hip) ---------------------------------------
+ * The statistic of the reference's core/submodules/gan_stability/metrics/inception_score.py on the classifier head that
+ * the FID weight file carries (NOT torchvision's ImageNet network, which the reference runs a second time).
+ * gz_classifier_logits: logits[i][c] = sum_k codes[i][k] weight[c][k] + bias[c] for fp64 row-major DEVICE arrays codes
+ * [n][d], weight [classes][d] (nn.Linear's layout), bias [classes] (may be null), logits [n][classes], on
+ * v_mfma_f64_16x16x4_f64, one workgroup per 64 x 64 tile with the whole reduction index inside it.  n, d and classes need
+ * no multiple of anything (indices outside are never dereferenced); row offsets are 64-bit.  Every entry is summed over k
+ * in k order; logits is written and never read; no workspace; one launch on `stream`.
+ * GZ_ERR_BAD_SHAPE: n, d or classes below 1, a null pointer (bias excepted), logits overlapping codes or weight;
+ * GZ_ERR_TOO_LARGE: more than 2^31 - 1 tiles, or an array beyond the address space (nothing is launched).
+ *
+ * gz_inception_score: scores[s] = exp(mean_i sum_c p_ic (log p_ic - log py_c)) for s < splits into `splits` DEVICE doubles,
+ * where split s is rows s (n / splits) .. (s + 1) (n / splits) - 1 of logits [n][classes] (the trailing n % splits rows are
+ * ignored), p_i = softmax(logits_i) stabilised by the row maximum and py = mean_i p_i over the split.  A class with p = 0
+ * contributes 0, as in scipy.stats.entropy; logits of +-800 give no NaN; a split of one row scores exactly 1.  classes has
+ * no cap (no row is kept in LDS).  Deterministic: no floating-point atomics, every sum in a fixed order (rows in order
+ * inside a block of 64 rows that never spans two splits, blocks in block order), neither `scores` nor the workspace
+ * (gz_inception_score_workspace_bytes bytes: two doubles per row, one double per class and block of 64 rows) has to be
+ * zeroed; two calls give equal bits.  Five launches on `stream`.
+ * GZ_ERR_BAD_SHAPE: n, classes or splits below 1, splits > n, a null pointer; GZ_ERR_TOO_LARGE: a grid beyond 2^31 - 1
+ * workgroups; GZ_ERR_WORKSPACE: workspace too short (nothing is launched; the size query returns 0 for a refused shape). */
+int gz_classifier_logits(const double* codes, long long n, int d, const double* weight, const double* bias,
+                         int classes, double* logits, hipStream_t stream);
+size_t gz_inception_score_workspace_bytes(long long n, int classes, int splits);
+int gz_inception_score(const double* logits, long long n, int classes, int splits, double* scores,
+                       void* workspace, size_t ws_bytes, hipStream_t stream);
+
 /* text of the last HIP error seen by a launcher on the calling thread ("" if none) */
 const char* gz_last_error(void);
 

@@ -20,6 +20,8 @@ gz_samples_to_inception_input), the network at a large batch, fp64 mean / covari
 csrc/gz_moments.hip) and KID's sums.  The matrix square root stays on the host unless ``fid_on_device`` asks for
 ``frechet_distance_device``: two Newton-Schulz square roots of symmetric positive semi-definite matrices, matrix products
 alone, on the fp64 MFMA product of csrc/gz_sqrtm.hip.  ``frechet_distance_newton_schulz`` is the same recurrence in numpy.
+With ``classifier=`` it also reports the Inception Score (gan_stability's metrics/inception_score.py) of the resident
+codes: ``inception_score_device`` on csrc/gz_inception_score.hip, ``inception_score_from_logits`` its host yardstick.
 """
 import numpy as np
 import torch
@@ -412,6 +414,99 @@ def feature_moments_device(codes):
     return mean, cov
 
 
+def inception_score_from_logits(logits, splits=10):
+    """Inception Score of classifier logits [n, classes] on the host in numpy fp64 -> (mean, std, split_scores): the loop
+    of the reference's core/submodules/gan_stability/metrics/inception_score.py:54-66 -- softmax over all classes,
+    contiguous splits of ``n // splits`` rows (the trailing ``n % splits`` rows are ignored), ``scipy.stats.entropy(p_i,
+    p_y)`` per row, ``exp(mean)`` per split, then mean and std over the splits.  The yardstick ``inception_score_device``
+    is measured against.
+
+    One deliberate difference from the reference lies in front of this function, not in it: the reference runs
+    torchvision's ImageNet InceptionV3 (1000 classes) over the images a second time; here the logits come from the
+    classifier head that the FID weight file carries (``FIDInceptionV3.fc``, 1008 classes of the 2015 network -- the one
+    the score was defined on) applied to the pool features the evaluation already holds."""
+    from scipy.stats import entropy
+    logits = np.asarray(logits, dtype=np.float64)
+    splits = int(splits)
+    if logits.ndim != 2 or splits < 1 or splits > logits.shape[0]:
+        raise ValueError("expected [n, classes] logits and 1 <= splits <= n, got %s and %d" % (logits.shape, splits))
+    e = np.exp(logits - logits.max(axis=1, keepdims=True))
+    preds = e / e.sum(axis=1, keepdims=True)
+    m = logits.shape[0] // splits
+    split_scores = []
+    for k in range(splits):
+        part = preds[k * m:(k + 1) * m]
+        py = np.mean(part, axis=0)
+        split_scores.append(np.exp(np.mean([entropy(part[i], py) for i in range(part.shape[0])])))
+    split_scores = np.asarray(split_scores)
+    return float(np.mean(split_scores)), float(np.std(split_scores)), split_scores
+
+
+def _fp64_device_codes(codes, what, instead):
+    if not isinstance(codes, torch.Tensor) or codes.dim() != 2 or codes.dtype != torch.float64:
+        raise ValueError("codes must be a float64 [n, d] tensor (eval.device_codes makes one)")
+    if not codes.is_cuda:
+        raise RuntimeError("lightning_gan_zoo_amd.eval: the device %s runs on the HIP kernels; device %r is not a GPU "
+                           "and there is no fallback (use %s)" % (what, codes.device, instead))
+    return codes if codes.is_contiguous() else codes.contiguous()
+
+
+def _classifier_on(device, weight, bias, d):
+    """(weight [classes, d], bias [classes] or None) as contiguous fp64 tensors on ``device`` (fp32 is widened: exact)."""
+    def fp64(t):
+        t = t if isinstance(t, torch.Tensor) else torch.from_numpy(np.array(t))
+        if t.dtype not in (torch.float32, torch.float64):
+            raise ValueError("the classifier's weight and bias must be float32 or float64, got %s" % t.dtype)
+        return t.detach().to(device).to(torch.float64).contiguous()
+    weight = fp64(weight)
+    if weight.dim() != 2 or weight.shape[1] != d:
+        raise ValueError("weight must be [classes, %d] (nn.Linear's layout), got %s" % (d, tuple(weight.shape)))
+    if bias is not None:
+        bias = fp64(bias)
+        if tuple(bias.shape) != (weight.shape[0],):
+            raise ValueError("bias must be [%d], got %s" % (weight.shape[0], tuple(bias.shape)))
+    return weight, bias
+
+
+def classifier_logits_device(codes, weight, bias=None):
+    """``codes @ weight.T + bias`` for fp64 device codes [n, d] as an fp64 device tensor [n, classes], on the fp64 MFMA
+    kernel (gz_classifier_logits, csrc/gz_inception_score.hip).  ``weight`` [classes, d] / ``bias`` [classes]: the
+    classifier head of the FID weight file (``FIDInceptionV3.fc`` -- not torchvision's ImageNet network, see
+    ``inception_score_from_logits``), float32 or float64 on any device, converted once.  No CPU fallback."""
+    from . import functional as F
+    from ._lib import check, lib
+    codes = _fp64_device_codes(codes, "classifier logits", "numpy's dot")
+    n, d = codes.shape
+    weight, bias = _classifier_on(codes.device, weight, bias, d)
+    classes = weight.shape[0]
+    with torch.cuda.device(codes.device):
+        logits = torch.empty((n, classes), dtype=torch.float64, device=codes.device)
+        check(lib.gz_classifier_logits(F._p(codes), n, d, F._p(weight), None if bias is None else F._p(bias), classes,
+                                       F._p(logits), F._stream()), "classifier_logits")
+    return logits
+
+
+def inception_score_device(codes, weight, bias=None, splits=10):
+    """``inception_score_from_logits(codes @ weight.T + bias, splits)`` on the device -> (mean, std, split_scores) as
+    floats and a numpy array: two C-ABI calls (gz_classifier_logits, gz_inception_score; csrc/gz_inception_score.hip),
+    the ``splits`` doubles copied back, their mean and std taken on the host.  The classifier is the head of the FID
+    weight file, not the reference's torchvision network (``inception_score_from_logits``).  No CPU fallback."""
+    from . import functional as F
+    from ._lib import check, lib
+    logits = classifier_logits_device(codes, weight, bias)
+    (n, classes), splits = logits.shape, int(splits)
+    if splits < 1 or splits > n:
+        raise ValueError("splits must lie in 1 .. n = %d, got %d" % (n, splits))
+    with torch.cuda.device(logits.device):
+        scores = torch.empty((splits,), dtype=torch.float64, device=logits.device)
+        ws_bytes = lib.gz_inception_score_workspace_bytes(n, classes, splits)
+        ws = torch.empty(max(ws_bytes, 8), dtype=torch.uint8, device=logits.device)
+        check(lib.gz_inception_score(F._p(logits), n, classes, splits, F._p(scores), F._p(ws), ws_bytes, F._stream()),
+              "inception_score")
+        split_scores = scores.cpu().numpy()
+    return float(np.mean(split_scores)), float(np.std(split_scores)), split_scores
+
+
 def _square_fp64_device(a, what):
     if not isinstance(a, torch.Tensor) or a.dim() != 2 or a.shape[0] != a.shape[1] or a.dtype != torch.float64:
         raise ValueError("%s must be a square float64 tensor" % what)
@@ -581,12 +676,16 @@ def _fid_on_device(real, mean, cov):
     return fid
 
 
-def evaluate_device(module, dump, net, real, batch=250, n_subsets=100, fid_on_device=False):
+def evaluate_device(module, dump, net, real, batch=250, n_subsets=100, fid_on_device=False, classifier=None,
+                    inception_splits=10):
     """``evaluate`` with everything between the generator and the metrics on the device: features at batch ``batch``
     into one resident fp64 tensor, mean / covariance through gz_feature_moments (only those two are copied to the host,
     for ``frechet_distance``), KID through ``polynomial_mmd_averages_device`` on the resident tensors -- the same subset
     draws from numpy's global generator.  ``real``: a ``RealStatistics``.  ``fid_on_device``: the moments stay on the
-    device and ``frechet_distance_device`` runs with the real set's cached root.  Returns the same dict as ``evaluate``."""
+    device and ``frechet_distance_device`` runs with the real set's cached root.  Returns the same dict as ``evaluate``.
+    ``classifier``: ``(weight, bias)`` of the classifier head in the FID weight file; the dict then gains ``"is"`` and
+    ``"is_std"``, the Inception Score over ``inception_splits`` splits of the same resident generated codes
+    (``inception_score_device`` -- the reference's statistic on that head, not on torchvision's ImageNet network)."""
     fake = device_activations(module, dump, net, batch)
     mean, cov = feature_moments_device(fake)
     if fid_on_device:
@@ -594,7 +693,11 @@ def evaluate_device(module, dump, net, real, batch=250, n_subsets=100, fid_on_de
     else:
         fid = frechet_distance(real.mu, real.sigma, mean.cpu().numpy(), cov.cpu().numpy())
     kid = polynomial_mmd_averages_device(real.codes, fake, n_subsets=n_subsets, device=fake.device)
-    return {"fid": fid, "kid": float(kid[0].mean()), "kid_std": float(kid[0].std())}
+    out = {"fid": fid, "kid": float(kid[0].mean()), "kid_std": float(kid[0].std())}
+    if classifier is not None:
+        weight, bias = classifier
+        out["is"], out["is_std"], _ = inception_score_device(fake, weight, bias, splits=inception_splits)
+    return out
 
 
 def evaluate(module, dump, feature_fn, real_act, n_subsets=100, kid_on_device=False, real_codes_device=None):

@@ -53,7 +53,11 @@ RUNNER_KEYS = {"max_steps": None, "log_every": 10, "dataset_path": None, "seed":
                # with eval_on_device: the Frechet distance's matrix square roots on the device too (Newton-Schulz on
                # csrc/gz_sqrtm.hip, eval.frechet_distance_device); within 1e-9 (rank-deficient statistics: 1e-7) of
                # tr S1 + tr S2 of the host value, which an evaluation whose iteration does not converge falls back to
-               "fid_on_device": False}
+               "fid_on_device": False,
+               # with eval_on_device: the Inception Score (gan_stability's metrics/inception_score.py, splits as there) of
+               # the generated codes the pass already holds, through the classifier head of the FID weight file
+               # (eval.inception_score_device, csrc/gz_inception_score.hip) -- not torchvision's ImageNet network
+               "inception_score": False, "inception_score_splits": 10}
 BUILTIN_DATASETS = ("synthetic", "image_folder", "tensor_file", "celeb_a", "mnist")
 AVERAGE_PREFIX = "generator_average."     # state_dict keys of the averaged generator's parameters, next to generator.*
 LIGHTNING_VERSION_TAG = "1.2.0"       # envelope layout written below (Lightning 1.1 / 1.2 generation)
@@ -93,6 +97,9 @@ def check_eval_keys(run):
     if run.get("fid_on_device", False) and not run.get("eval_on_device", False):
         raise SystemExit("fid_on_device=true is honoured only together with eval_on_device=true: the device Frechet "
                          "distance reads the moments the device evaluation pass leaves on the GPU")
+    if run.get("inception_score", False) and not run.get("eval_on_device", False):
+        raise SystemExit("inception_score=true is honoured only together with eval_on_device=true: the device Inception "
+                         "Score reads the codes the device evaluation pass leaves on the GPU")
 
 
 def _builtin_dataset(name, run, filepaths):
@@ -711,19 +718,29 @@ def wants_fid(cfg, run):
 
 
 def device_fid_evaluator(dump, features, real_act, device, batch=250, average=None, mu=None, sigma=None,
-                         fid_on_device=False):
+                         fid_on_device=False, inception_score=False, inception_splits=10):
     """The ``evaluate`` hook of fit() on the device pass (eval.evaluate_device).  The real set's device codes and its
     mean / covariance (``mu`` / ``sigma`` when a cache file holds them, else one moments launch) are made here, once per
     run; every epoch then costs the generated set alone.  ``fid_on_device``: the Frechet distance on the device as well
-    (the real covariance's square root is made by the first evaluation and kept)."""
+    (the real covariance's square root is made by the first evaluation and kept).  ``inception_score``: the Inception
+    Score over ``inception_splits`` splits as well, through the classifier head of the weight file (``features.net.fc``,
+    widened to fp64 on the device here, once per run; not the reference's torchvision network:
+    eval.inception_score_from_logits); the best checkpoint stays chosen by FID."""
     from . import eval as E
     real = E.RealStatistics(real_act, device, mu=mu, sigma=sigma)
     extra = {"fid_on_device": True} if fid_on_device else {}
+    if inception_score:
+        fc = features.net.fc
+        extra["classifier"] = tuple(t.detach().to(device).to(torch.float64).contiguous() for t in (fc.weight, fc.bias))
+        extra["inception_splits"] = int(inception_splits)
 
     def evaluate(mod, epoch):
         with rendering_from(mod, average):          # generator_average=true: the averaged generator is what is scored
             m = E.evaluate_device(mod, dump, features.device, real, batch=batch, **extra)
-        print("epoch %d FID: %.4f KID mean: %.6f KID stddev: %.6f" % (epoch, m["fid"], m["kid"], m["kid_std"]))
+        line = "epoch %d FID: %.4f KID mean: %.6f KID stddev: %.6f" % (epoch, m["fid"], m["kid"], m["kid_std"])
+        if inception_score:
+            line += " IS: %.4f +- %.4f" % (m["is"], m["is_std"])
+        print(line)
         return m
 
     return evaluate
@@ -755,9 +772,12 @@ def make_fid_evaluator(cfg, run, module, device, average=None):
     real_act = real_activations(val_root, features)
     if run.get("eval_on_device", False):
         mu, sigma = real_statistics_cache(val_root)
+        score = {}
+        if run.get("inception_score", False):
+            score = {"inception_score": True, "inception_splits": int(run.get("inception_score_splits", 10))}
         return device_fid_evaluator(dump, features, real_act, device, batch=int(run.get("eval_batch_size", 250)),
                                     average=average, mu=mu, sigma=sigma,
-                                    fid_on_device=bool(run.get("fid_on_device", False)))
+                                    fid_on_device=bool(run.get("fid_on_device", False)), **score)
     kid_on_device = bool(run.get("kid_on_device", False))
     # real_act is the same every epoch: its fp64 device copy is made once per run, here
     real_codes = E.device_codes(real_act, device) if kid_on_device else None

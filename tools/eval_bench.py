@@ -23,6 +23,12 @@ Per sample count n the one JSON line holds
   * ``moments_ms`` / ``moments_fp64_tflops`` / ``np_cov_s``  the moments launch sequence by HIP events (median of
                            ``--reps`` after two warm-ups; FLOP = 2 n d^2 / 2 * (1 + 1/tiles): the upper-triangle tiles the
                            kernel executes) beside numpy's np.cov of the same array;
+  * ``inception_score_s`` / ``inception_score_host_s``  eval.inception_score_device on the resident [n, 2048] codes with a
+                           seeded 1008-class head (median wall time of ``--reps`` calls after a warm-up) beside the host's
+                           way to the same score: ``codes.cpu()``, a numpy product, eval.inception_score_from_logits
+                           (once); ``inception_score_rel_diff`` the largest relative difference of a split score,
+                           ``logits_ms`` / ``logits_fp64_tflops`` gz_classifier_logits alone by HIP events (FLOP =
+                           2 n 2048 1008);
 and once: ``input_fused_us`` beside ``input_resize_us``: gz_samples_to_inception_input against gz_resize_bilinear alone on
 the same [250, 3, 64, 64] -> 299 x 299 shape (events, median of 20 after 5 warm-ups).
 All wall times follow a warm-up pass (clocks, allocator, folded weights) and end with a device synchronisation.
@@ -122,6 +128,37 @@ def product_record(d, reps):
             "product_pair_ms": round(two, 3), "product_pair_fp64_tflops": round(2 * flop / two / 1e9, 2)}
 
 
+def inception_score_record(codes, reps, classes=1008, splits=10):
+    """``inception_score_s``: eval.inception_score_device on the resident codes (a warm-up call, then the median wall
+    time of ``reps`` calls, each ending in its own copy-back of the split scores); ``inception_score_host_s``: what the
+    same score costs without the kernels -- ``codes.cpu()``, numpy's product with the head and
+    eval.inception_score_from_logits, once.  A seeded classifier head, scaled so that the logits differ by a few units
+    from row to row and centred by its bias (uncentred, the features' common mean hands every row to one class and the
+    score is 1.00 whatever the rows are); converted once per run, as the runner does."""
+    n, d = codes.shape
+    g = torch.Generator().manual_seed(7)
+    w64 = torch.randn(classes, d, generator=g, dtype=torch.float64).cuda()
+    mean = codes.mean(dim=0)
+    w64 *= 2.5 / float(((codes[:2000] - mean) @ w64.T).std())
+    b64 = 0.1 * torch.randn(classes, generator=g, dtype=torch.float64).cuda() - w64 @ mean
+    E.inception_score_device(codes, w64, b64, splits)
+    times = []
+    for _ in range(reps):
+        t, dev = wall(lambda: E.inception_score_device(codes, w64, b64, splits))
+        times.append(t)
+    logits_ms = events_ms(lambda: E.classifier_logits_device(codes, w64, b64), reps, 1)
+
+    def host():
+        x = codes.cpu().numpy()
+        return E.inception_score_from_logits(x.dot(w64.cpu().numpy().T) + b64.cpu().numpy(), splits)
+
+    t_host, want = wall(host)
+    return {"inception_score_s": round(float(np.median(times)), 4), "inception_score_host_s": round(t_host, 3),
+            "inception_score": dev[0], "inception_score_std": dev[1],
+            "inception_score_rel_diff": float(np.abs(dev[2] / want[2] - 1).max()),
+            "logits_ms": round(logits_ms, 3), "logits_fp64_tflops": round(2.0 * n * d * classes / logits_ms / 1e9, 2)}
+
+
 def input_record():
     N, C, H, W, OH, OW = 250, 3, 64, 64, 299, 299
     x = torch.rand(N, C, H, W, device="cuda") * 1.4 - 0.2
@@ -194,6 +231,7 @@ def main():
         run.update(product_record(mean.shape[0], a.reps))
         del mu1, sigma1, root1
         run.update(moments_record(fake[0], a.reps))
+        run.update(inception_score_record(fake[0], a.reps))
         del fake
         if n in a.host_n:
             np.random.seed(1)
