@@ -192,10 +192,11 @@ static int run_fwd(const float* x, const float* wp, const float* bias, float* y,
 }
 
 // k4 s2 p1 forward convolution on the igemm2 skeleton (raw input rows by LDS-DMA, taps on the fragment read)
-template <class Cfg, int OWC>
+// (PS: the pad-skip form of the loader, 4x4 output maps -- run_fwd2_ow)
+template <class Cfg, int OWC, bool PS = false>
 static int run_fwd2(const float* x, const float* wp, const float* bias, float* y, const ConvShape& s, int act,
                     float slope, hipStream_t st, int splits, float* slab, float* stats) {
-    using AL = ConvFwdA2<Cfg::BM, OWC>;
+    using AL = ConvFwdA2<Cfg::BM, OWC, PS>;
     using BL = MContigB2<Cfg::BN>;
     typename AL::Params pa{x, s, make_fastdiv(s.OH * s.OW), make_fastdiv(s.OW)};
     const int M = s.N * s.OH * s.OW;
@@ -246,7 +247,13 @@ template <class Cfg>
 static int run_fwd2_ow(const float* x, const float* wp, const float* bias, float* y, const ConvShape& s, int act,
                        float slope, hipStream_t st, int splits, float* slab, float* stats) {
     switch (s.OW) {
-        case 4: return run_fwd2<Cfg, 4>(x, wp, bias, y, s, act, slope, st, splits, slab, stats);
+        case 4:
+            // 4x4 maps on 128-pixel wave tiles of at most 64 columns: the MFMAs on rows that are padding only are left out
+            if constexpr (Cfg::TN <= 2) {
+                if (s.OH == 4 && !knobs().no_padskip)
+                    return run_fwd2<Cfg, 4, true>(x, wp, bias, y, s, act, slope, st, splits, slab, stats);
+            }
+            return run_fwd2<Cfg, 4>(x, wp, bias, y, s, act, slope, st, splits, slab, stats);
         case 8: return run_fwd2<Cfg, 8>(x, wp, bias, y, s, act, slope, st, splits, slab, stats);
         case 16: return run_fwd2<Cfg, 16>(x, wp, bias, y, s, act, slope, st, splits, slab, stats);
         case 32: return run_fwd2<Cfg, 32>(x, wp, bias, y, s, act, slope, st, splits, slab, stats);
@@ -448,13 +455,18 @@ static int run_dgrad(const float* y, const float* wp, const float* bias, float* 
 }
 
 // k4 s2 p1 transposed convolution on the igemm2 skeleton (row-shared A rows by LDS-DMA, packed per-phase weights)
-template <class Cfg>
+// (PS: the pad-skip form of the loader, 4x4 feature maps)
+template <class Cfg, bool PS = false>
 static int run_dgrad2(const float* y, const float* wp, const float* bias, float* x, const ConvShape& s, int act,
                       float slope, hipStream_t st, int splits, float* slab, float* stats) {
-    using AL = ConvDgA2<Cfg::BM>;
+    using AL = ConvDgA2<Cfg::BM, PS>;
     using BL = MContigB2<Cfg::BN>;
     using Epi = EpiPhaseB<2>;
     const int AH = s.H / 2, AW = s.W / 2;
+    if constexpr (!PS && Cfg::BM == 256 && Cfg::TN <= 2) {
+        if (AH == 4 && AW == 4 && !knobs().no_padskip)
+            return run_dgrad2<Cfg, true>(y, wp, bias, x, s, act, slope, st, splits, slab, stats);
+    }
     typename AL::Params pa{y, s, AH, AW, make_fastdiv(AH * AW), make_fastdiv(AW)};
     const int Kg = s.K * 4;
     const int ldc = round4(s.C);

@@ -102,13 +102,45 @@ struct MContigB2 {
     }
 };
 
+// ---- pad-skip forms of the two k4 s2 p1 row loaders on 4x4 maps (ConvFwdA2<256, 4, true>, ConvDgA2<256, true>) -------
+// Vertical padding arrives as zero LDS rows (out-of-range LDS-DMA lanes) and flows through the matrix pipe.  With
+// m = (image, row, column) and 16 pixels per image, a 32-row MFMA block is two whole images: padded rows in every block
+// for every vertical tap, no block that is padding only.  These forms stage a wavefront's 128 pixels (8 images) in the
+// order (row, image, column): LDS position  wm*128 + i*32 + g*4 + b  holds pixel  (8*wm + g)*16 + 4*i + b  -- block i of a
+// wavefront is map row i of its eight images -- by permuting which 16-byte quad a lane of a piece FETCHES (a quad is one
+// map row at width 4; where it lands in LDS, the fragment addresses and their banks stay what they were).  A (block,
+// k-step) whose vertical tap lies outside the map is then a compile-time entry (skip_mask: bit i = block i): its
+// fragment read and its MFMAs are not issued, one in eight.  igemm2_kernel puts the accumulators back in pixel order
+// (unpermute_padskip) before anything reads them, so every output is the same products in the same order; the dropped
+// terms are +-0 added to an accumulator that is never -0.  (One deviation: a non-finite weight no longer meets the
+// padding's zero, 0 * Inf = NaN, on those taps.)
+__device__ __forceinline__ int padskip_quad(int q) {       // LDS quad (= forward-row segment) position -> the one staged there
+    return (((q >> 5) << 3 | (q & 7)) << 2) | ((q >> 3) & 3);
+}
+template <class AL, class = void>
+struct is_padskip : std::false_type {};
+template <class AL>
+struct is_padskip<AL, std::enable_if_t<AL::PADSKIP>> : std::true_type {};
+
 // A operand of the k4 s2 p1 TRANSPOSED convolution, row-shared like ConvDgALoaderRow4 (a chunk's image is 8 rows =
 // 4 feature channels x 2 vertical taps of UNSHIFTED feature rows; the horizontal tap is applied on the fragment
 // read, the one column a shifted read takes from the neighbouring row is zeroed in the register).  One piece = one
 // LDS row of 256 pixels; wavefront w stages channel w of the chunk, its two vertical taps.
-template <int BM>
+// PS: the pad-skip form above (AH = AW = 4, chosen by the launcher).
+template <int BM, bool PS = false>
 struct ConvDgA2 {
     static_assert(BM == 256 || BM == 512, "whole 256-pixel pieces per LDS row");
+    static_assert(!PS || BM == 256, "pad-skip: a wavefront's 128 pixels are 8 whole 4x4 maps");
+    static constexpr bool PADSKIP = PS;
+    // k-step S has vertical tap ty = S & 1, feature row a + (py + 1) / 2 - ty: output rows of parity py = 0 have no row
+    // above a = 0 (ty = 1), those of parity 1 none below a = 3 (ty = 0).  py is a launch-time fact of the workgroup, so
+    // parity 1 stages its map rows in REVERSE order (block i = row 3 - i): it is block 0 either way, in the odd k-steps
+    // for py = 0 and in the even ones for py = 1 -- a wave-uniform branch around block 0's MFMA (one loop per parity
+    // spilled in the epilogue; gz_igemm2.h igemm2_kernel).
+    static constexpr bool SKIP_BLOCK0_BY_PARITY = PS;
+    static constexpr unsigned skip_mask(int mode, int S) { return 0u; }
+    __device__ __forceinline__ int block0_skip_parity() const { return 1 - py_; }      // k-steps with S & 1 == this
+    __device__ __forceinline__ int block_mirror() const { return py_ ? 3 : 0; }         // block i holds map row i ^ this
     using Params = typename ConvDgALoader<BM, 4, 4, 2, 1>::Params;
     // LDS rows carry 4 pad floats that are zeroed once and never written again: a lane whose shifted read would take
     // its value from the neighbouring image row reads that column instead (no v_cndmask in the loop -- an f32 MFMA
@@ -120,7 +152,7 @@ struct ConvDgA2 {
     static constexpr bool ROWSHARE = true;
     __amdgpu_buffer_rsrc_t rsrc;
     uint32_t voff[2 * PPR];       // [vertical tap][256-pixel block]
-    int wave, K, OHW, shift_half1;
+    int wave, K, OHW, shift_half1, py_;
     __device__ __forceinline__ void init(const Params& p, int tile, int phase, int tid) {
         const ConvShape& s = p.s;
         rsrc = make_rsrc(p.y, (uint32_t)s.N * s.K * s.OH * s.OW * 4u);
@@ -129,9 +161,10 @@ struct ConvDgA2 {
         K = s.K; OHW = s.OH * s.OW;
         const int py = phase / 2, px = phase % 2;
         shift_half1 = (px + 1) / 2 - 1;
+        py_ = py;
 #pragma unroll
         for (int hb = 0; hb < PPR; ++hb) {
-            const uint32_t m = (uint32_t)tile * BM + hb * 256 + lane * 4;
+            const uint32_t m = (uint32_t)tile * BM + hb * 256 + (PS ? padskip_quad(lane) ^ (py ? 3 : 0) : lane) * 4;
             const bool m_ok = m < (uint32_t)s.N * p.AH * p.AW;
             const uint32_t n = fdiv(m, p.div_ahw);
             const uint32_t pix = m - n * (uint32_t)(p.AH * p.AW);
@@ -159,9 +192,16 @@ struct ConvDgA2 {
 // OW is a template parameter so that the row step 2*OW sits in the ds_read's immediate offset (no VALU in the loop);
 // the column left of the image (ox = 0, kx = 0) and right of it (ox = OW-1, kx = 3) are read from a zeroed region
 // behind the image instead of being masked in registers.  Needs W = 2*OW, H = 2*OH, BM % OW == 0, 16-byte alignment.
-template <int BM, int OWC>
+// PS: the pad-skip form above (OH = OW = 4, chosen by the launcher).
+template <int BM, int OWC, bool PS = false>
 struct ConvFwdA2 {
     static_assert(BM == 256 && BM % OWC == 0 && OWC >= 2, "piece mapping");
+    static_assert(!PS || OWC == 4, "pad-skip: a wavefront's 128 pixels are 8 whole 4x4 maps");
+    static constexpr bool PADSKIP = PS;
+    // k-step S has ky = S >> 1, input row 2 * oy - 1 + ky: above the image for (oy = 0, ky = 0), below it for (3, 3)
+    static constexpr bool SKIP_BLOCK0_BY_PARITY = false;
+    static constexpr unsigned skip_mask(int mode, int S) { return (S < 2 ? 1u : 0u) | (S >= 6 ? 8u : 0u); }
+    __device__ __forceinline__ int block_mirror() const { return 0; }
     using Params = typename ConvFwdALoader<BM, 4, 4, 2, 1>::Params;
     static constexpr int LD = BM, ROWS = BK / 2, PIECES = 2;
     static constexpr int OW_C = OWC;
@@ -182,7 +222,7 @@ struct ConvFwdA2 {
             const int f = ((wave * 2 + q) * 64 + lane) * 4;
             const int seg = f / (8 * OWC), rem = f - seg * 8 * OWC;
             const int ky = rem / (2 * OWC), col = rem - ky * 2 * OWC;
-            const uint32_t m = (uint32_t)tile * BM + seg * OWC;           // first pixel of the segment
+            const uint32_t m = (uint32_t)tile * BM + (PS ? padskip_quad(seg) : seg) * OWC;       // first pixel of the segment
             const bool m_ok = m < (uint32_t)s.N * s.OH * s.OW;
             const uint32_t n = fdiv(m, p.div_ohw);
             const uint32_t oy = fdiv(m - n * (uint32_t)(s.OH * s.OW), p.div_ow);
@@ -572,6 +612,53 @@ constexpr int step_brow_of(int m, int S) {         // first row of the B image k
     if constexpr (is_dualmode<AL>::value) return AL::step_brow(m, S);
     else return 2 * S;
 }
+// pad-skip loaders: the accumulator blocks (bit i = block i of the wavefront) whose rows are all padding at k-step S of
+// a chunk, in skip mode m; m < 0 and every other loader: none
+template <class AL>
+constexpr unsigned skip_mask_of(int m, int S) {
+    if constexpr (is_padskip<AL>::value) return m < 0 ? 0u : AL::skip_mask(m, S);
+    else return 0u;
+}
+template <class AL>
+constexpr bool skip_block0_by_parity() {           // ... block 0 in the k-steps of one parity, known at launch time
+    if constexpr (is_padskip<AL>::value) return AL::SKIP_BLOCK0_BY_PARITY;
+    else return false;
+}
+
+// Pad-skip loaders: back to pixel order.  Block i of lane (half, l32) holds wavefront pixel (l32 >> 2) * 16 + 4 i + (l32 & 3)
+// (i ^ mirror for i: ConvDgA2's reversed rows); block i', lane (half, l') must hold pixel 32 i' + l', which is block
+// (l' >> 2) & 3 of lane (half, 8 i' + 4 (l' >> 4) + (l' & 3)).
+// Through LDS, eight accumulator registers of the four blocks at a time: slot [q = block * 8 + register][thread], the
+// wavefront's own 64 columns of `buf` (32 * NT floats) -- no other wavefront reads or writes them, and a wavefront's
+// LDS operations complete in order, so no barrier between the passes.  The lane index is XORed with 8 * block on the
+// way in: writes and reads both touch 32 different banks per 32-lane half.
+template <int TM, int TN>
+__device__ __forceinline__ void unpermute_padskip(f32x16 (&acc)[TM][TN], float* buf, int tid, int mirror) {
+    static_assert(TM == 4, "four 32-row blocks per wavefront");
+    constexpr int PR = 8;                           // accumulator registers per block and pass
+    const int lane = tid & 63;
+    float* const col = buf + (tid & ~63);
+    const int sb = ((lane >> 2) & 3) ^ mirror;                             // source block
+    const int sl = (lane & 32) | ((lane >> 4) & 1) << 2 | (lane & 3);      // source lane, without 8 i'
+#pragma unroll
+    for (int j = 0; j < TN; ++j) {
+#pragma unroll
+        for (int r0 = 0; r0 < 16; r0 += PR) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+#pragma unroll
+                for (int r = 0; r < PR; ++r) col[(i * PR + r) * NT + (lane ^ (i << 3))] = acc[i][j][r0 + r];
+            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+#pragma unroll
+                for (int r = 0; r < PR; ++r) acc[i][j][r0 + r] = col[(sb * PR + r) * NT + ((sl | i << 3) ^ (sb << 3))];
+            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+        }
+    }
+}
 
 // KG = 2 (round 5): TWO wave groups of four wavefronts in one 512-thread workgroup work on the SAME output tile, each on
 // half of the workgroup's reduction range with an LDS ring of its own, and meet in LDS at the end (group 1 parks its
@@ -637,6 +724,15 @@ __global__ __launch_bounds__(NT * KG, KG == 1 ? Cfg::OCC : 2) void igemm2_kernel
     // and the accumulator blocks (output phases) its MFMAs feed -- AL::mode_plain(m), AL::mode_mask(m), al.bound[]
     constexpr bool DM = is_dualmode<AL>::value;
     static_assert(!DM || (RS && KG == 1 && (TN == 2 || TN == 4)), "multi-mode: row-shared loader, phases in the accumulator blocks");
+    // pad-skip loaders (4x4 maps): blocks uniform in the map row, (block, k-step) pairs that are padding only left out
+    // (skip_mask_of: compile-time entries; PSB: block 0 in the k-steps of one parity, a wave-uniform branch),
+    // accumulators back in pixel order before the epilogue
+    constexpr bool PSK = is_padskip<AL>::value;
+    constexpr bool PSB = skip_block0_by_parity<AL>();
+    static_assert(!PSK || ((RS || FR) && !DM && TM == 4 && TN <= 2 && Cfg::BM == 256 && Cfg::WM == 2),
+                  "pad-skip: 128-pixel wave tiles of a 256-pixel workgroup tile");
+    static_assert(!PSK || igemm2_lds_bytes_at<Cfg, AL, BL, KG>(igemm2_depth<Cfg, AL, BL, KG>()) >= (size_t)32 * NT * 4,
+                  "pad-skip: the un-permute's 32 slots per thread");
     constexpr int A_EXTRA = igemm2_a_extra<AL>();
     constexpr int A_ELEMS = AL::ROWS * LDA + A_EXTRA, B_ELEMS = BL::ROWS * LDB;
     constexpr int STAGE = A_ELEMS + B_ELEMS;
@@ -798,9 +894,10 @@ __global__ __launch_bounds__(NT * KG, KG == 1 ? Cfg::OCC : 2) void igemm2_kernel
             else fetch_m(std::integral_constant<int, 0>{}, std::integral_constant<int, 1>{}, so, af, bf);
         }
     };
-    auto fetch = [&](auto Sc, uint32_t so, float (&af)[TM], float (&bf)[TN]) {
-        // (k-step Sc of the GROUP: chunk JO / (STAGE * 4) of it, that chunk's k-step S)
+    auto fetch = [&](auto Sc, auto Kc, uint32_t so, float (&af)[TM], float (&bf)[TN]) {
+        // (k-step Sc of the GROUP: chunk JO / (STAGE * 4) of it, that chunk's k-step S; skip mode Kc, < 0: every block)
         constexpr int S = decltype(Sc)::value % STEPS, JO = decltype(Sc)::value / STEPS * STAGE * 4;
+        constexpr unsigned SK = skip_mask_of<AL>(decltype(Kc)::value, S);
         constexpr int AO = (RS ? LDA : 2 * LDA) * S * 4 + JO, BO = 2 * S * LDB * 4 + JO;
         static_assert(AO + 2 * LDA * 4 < 65536 && BO + 512 < 65536, "ds_read immediate offsets");
 #ifdef GZ2_EXP_NOFETCH
@@ -809,15 +906,15 @@ __global__ __launch_bounds__(NT * KG, KG == 1 ? Cfg::OCC : 2) void igemm2_kernel
         // immediate offsets only: no VALU address arithmetic inside the loop (`a_addr[i] + so` is per-chunk)
         if constexpr (FR) {
             constexpr int FO = (S >> 1) * 2 * fwd_ow<AL>() * 4 + JO;
-            af[0] = lds_rd<FO>(((S & 1) ? a_odd[0] : a_addr[0]) + so);
+            if constexpr (!(SK & 1u)) af[0] = lds_rd<FO>(((S & 1) ? a_odd[0] : a_addr[0]) + so);
             af[1] = lds_rd<FO>(((S & 1) ? a_odd[1] : a_addr[1]) + so);
             af[2] = lds_rd<FO>(((S & 1) ? a_odd[2] : a_addr[2]) + so);
-            af[3] = lds_rd<FO>(((S & 1) ? a_odd[3] : a_addr[3]) + so);
+            if constexpr (!(SK & 8u)) af[3] = lds_rd<FO>(((S & 1) ? a_odd[3] : a_addr[3]) + so);
         } else {
-            af[0] = lds_rd<AO>(a_addr[0] + so);
+            if constexpr (!(SK & 1u)) af[0] = lds_rd<AO>(a_addr[0] + so);
             af[1] = lds_rd<AO>(a_addr[1] + so);
             af[2] = lds_rd<AO>(a_addr[2] + so);
-            af[3] = lds_rd<AO>(a_addr[3] + so);
+            if constexpr (!(SK & 8u)) af[3] = lds_rd<AO>(a_addr[3] + so);
         }
         {
         bf[0] = lds_rd<BO>(b_addr + so);
@@ -860,11 +957,23 @@ __global__ __launch_bounds__(NT * KG, KG == 1 ? Cfg::OCC : 2) void igemm2_kernel
                 for (int j = 0; j < TN; ++j) bf[q][j] = 0.f;
             fetch_first(kc0, 0u, af[0], bf[0]);
         } else {
-            fetch(std::integral_constant<int, 0>{}, 0u, af[0], bf[0]);
+            if constexpr (PSK) {          // (a skipped block's fragment register is never read; it must still be a value)
+#pragma unroll
+                for (int q = 0; q < 2; ++q)
+#pragma unroll
+                    for (int i = 0; i < TM; ++i) af[q][i] = 0.f;
+            }
+            fetch(std::integral_constant<int, 0>{}, std::integral_constant<int, -1>{}, 0u, af[0], bf[0]);
         }
         lgkm_done(af[0], bf[0]);
         mask(af[0]);
         int stage = 0;
+        // (pad-skip, transposed form: block 0 is padding only in the k-steps of one parity)
+        bool b0_odd = true, b0_even = true;
+        if constexpr (PSB) {
+            b0_odd = al.block0_skip_parity() == 0;
+            b0_even = !b0_odd;
+        }
         // (dual mode: the row-shared chunks and the plain chunks are TWO loops, one after the other -- a per-chunk branch
         // between the two k-step forms inside one loop made the register allocator spill accumulators in every iteration)
         auto run_chunks = [&](int k_from, int k_to, auto Mc) {
@@ -879,6 +988,8 @@ __global__ __launch_bounds__(NT * KG, KG == 1 ? Cfg::OCC : 2) void igemm2_kernel
                 constexpr int S = decltype(Sc)::value;
                 constexpr int MD = decltype(Mc)::value;          // multi-mode loaders: this loop's k-step form
                 constexpr int c = S & 1, n = c ^ 1;
+                constexpr unsigned SK = skip_mask_of<AL>(MD, S % STEPS);      // pad-skip loaders: blocks left out (0 or 3)
+                static_assert((SK & ~9u) == 0, "the k-step leaves out block 0 or block 3");
                 auto mfma_row = [&](f32x16 (&cc)[TN], float a, const float (&b)[TN]) {
                     if constexpr (DM) {           // the accumulator blocks (output phases) this mode's taps feed
                         constexpr unsigned MK = mode_mask_of<AL>(MD, S);
@@ -891,9 +1002,14 @@ __global__ __launch_bounds__(NT * KG, KG == 1 ? Cfg::OCC : 2) void igemm2_kernel
                         }
                     } else gz::mfma_row(cc, a, b);
                 };
+                auto block0 = [&]() {
+                    if constexpr (PSB) {
+                        if ((S & 1) ? b0_odd : b0_even) mfma_row(acc[0], af[c][0], bf[c]);
+                    } else if constexpr (!(SK & 1u)) mfma_row(acc[0], af[c][0], bf[c]);
+                };
                 auto fetch_same = [&](auto S2c, uint32_t o, float (&fa)[TM], float (&fb)[TN]) {
                     if constexpr (DM) fetch_m(S2c, Mc, o, fa, fb);
-                    else fetch(S2c, o, fa, fb);
+                    else fetch(S2c, Mc, o, fa, fb);
                 };
                 // the pieces of group kc+DEPTH-BI go out in the FIRST k-steps, PPS per step, one behind each MFMA row
                 // (the stages they overwrite were last read in group kc-BI, behind its barrier), so that by the last
@@ -907,19 +1023,20 @@ __global__ __launch_bounds__(NT * KG, KG == 1 ? Cfg::OCC : 2) void igemm2_kernel
                 };
                 if constexpr (S + 1 < GSTEPS) {
                     fetch_same(std::integral_constant<int, S + 1>{}, so, af[n], bf[n]);
-                    mfma_row(acc[0], af[c][0], bf[c]);
+                    block0();
                     pieces(std::integral_constant<int, 0>{});
                     mfma_row(acc[1], af[c][1], bf[c]);
                     pieces(std::integral_constant<int, 1>{});
                     if constexpr (TM == 4) mfma_row(acc[2], af[c][2], bf[c]);
                     pieces(std::integral_constant<int, 2>{});
-                    if constexpr (TM == 4) mfma_row(acc[3], af[c][3], bf[c]);
+                    if constexpr (TM == 4 && !(SK & 8u)) mfma_row(acc[3], af[c][3], bf[c]);
                     pieces(std::integral_constant<int, 3>{});
                 } else {
                     // last k-step: half of its MFMAs, then group kc+BI must have landed (all but the NWAIT pieces of
                     // the groups behind it) and every wavefront must be done with this group's fragments; the first
                     // fragments of chunk kc+BI are fetched under the other half
-                    mfma_row(acc[0], af[c][0], bf[c]);
+                    // (pad-skip: the half that loses an MFMA keeps its other one -- blocks 0, 1 in front, 2, 3 behind)
+                    block0();
                     pieces(std::integral_constant<int, 0>{});
                     if constexpr (TM == 4) mfma_row(acc[1], af[c][1], bf[c]);
                     pieces(std::integral_constant<int, 1>{});
@@ -945,10 +1062,10 @@ __global__ __launch_bounds__(NT * KG, KG == 1 ? Cfg::OCC : 2) void igemm2_kernel
                     }
 #endif
                     if constexpr (DM) fetch_first(kc + BI, sno, af[n], bf[n]);     // the next chunk's, in ITS mode
-                    else fetch(std::integral_constant<int, 0>{}, sno, af[n], bf[n]);
+                    else fetch(std::integral_constant<int, 0>{}, Mc, sno, af[n], bf[n]);
                     if constexpr (TM == 4) {
                         mfma_row(acc[2], af[c][2], bf[c]);
-                        mfma_row(acc[3], af[c][3], bf[c]);
+                        if constexpr (!(SK & 8u)) mfma_row(acc[3], af[c][3], bf[c]);
                     } else {
                         mfma_row(acc[1], af[c][1], bf[c]);
                     }
@@ -1033,6 +1150,12 @@ __global__ __launch_bounds__(NT * KG, KG == 1 ? Cfg::OCC : 2) void igemm2_kernel
             for (int j = 0; j < TN; ++j)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) acc[i][j][r] += park[((i * TN + j) * 16 + r) * NT + tid];
+    }
+    if constexpr (PSK) {
+        // KG = 1: every wavefront is done with the rings.  KG = 2: the slots are columns of the park that only this
+        // wavefront's counterpart wrote and only this wavefront read.
+        if constexpr (KG == 1) __syncthreads();
+        unpermute_padskip<TM, TN>(acc, smem2, tid, al.block_mirror());
     }
 #ifdef GZ2_EXP_NOSTORE   // timing experiment: keep one store so the accumulators stay live
     if (acc[0][0][0] == 123456.789f)

@@ -31,6 +31,7 @@ namespace gz {
     X(int, igemm2_tile, "GZ_IGEMM2_TILE", 0)                /* 128 / 256: force the igemm2 N tile */                 \
     X(bool, no_tile64, "GZ_NO_TILE64", false)               /* round 4's 256x64 igemm2 tile off */                   \
     X(bool, no_kg2, "GZ_NO_KG2", false)                     /* round 5's two wave groups per workgroup off */        \
+    X(bool, no_padskip, "GZ_NO_PADSKIP", false)             /* 4x4 maps: padding rows through the matrix pipe, as before the pad-skip loaders */ \
     X(bool, no_pool_plane, "GZ_NO_POOL_PLANE", false)       /* evaluation path: the flat pooling kernel (round 5) */        \
     X(bool, no_pool_group, "GZ_NO_POOL_GROUP", false)       /* evaluation path: no compile-time-window pooling */           \
     X(bool, no_any2, "GZ_NO_ANY2", false)                   /* evaluation path: run-time geometries on igemm_kernel only (round 5) */ \
