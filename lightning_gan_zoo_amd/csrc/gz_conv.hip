@@ -28,7 +28,7 @@ namespace gz {
 
 // (TileId, Kind, Loader, Facts and Choice -- what choose_fwd / choose_dgrad / choose_wgrad, below after the run_*
 // functions they pick from, return -- are in gz_conv_choice.h, shared with gz_conv3d.hip; the tile configurations in
-// gz_igemm.h)
+// gz_igemm.h, which also lists the headers of the two skeletons by role)
 
 // Which launches take the igemm2 skeleton: its workgroup is a whole CU's worth of matrix pipes (one wavefront per
 // SIMD), so 256 tiles already fill the chip and anything from there up runs at the loop's rate; fewer would leave
@@ -575,7 +575,7 @@ static SplitPlan dgradtap2_plan(const ConvShape& s) {
     return SplitPlan{T256x128, splits < 1 ? 1 : splits};
 }
 
-// ---- 5x5 s2 p2 transposed convolution on row-shared LDS rows, all four output phases per workgroup (gz_igemm2.h:
+// ---- 5x5 s2 p2 transposed convolution on row-shared LDS rows, all four output phases per workgroup (gz_igemm2_loaders.h:
 // ConvDg5A2, DgQuadB2, EpiPhaseQuadB; round 6).  Tile = 256 pixels x 32 channels x (py, px); columns N = 4 C, one grid
 // phase; 3 K/8 chunks of 12 k-steps, every workgroup identical.  Unsplit when every CU gets a workgroup, else the
 // reduction is cut for ~512 workgroups (slabs + the finish pass).  Launches with little work per CU stay on the gather

@@ -27,13 +27,20 @@
 //   struct Params;
 //   void store(const Params&, acc, m_base, n_base, lane, y, z);
 //
-// The core is split over four headers (round 5; one 3.7 k-line file before), each including the one before it:
-//   gz_igemm_loaders.h    primitives (raw buffer loads, LDS-DMA), TileCfg, the round-1/2 operand loaders
+// The core is split by role (one 3.7 k-line file before round 5), this header being the one the .hip units include:
+//   gz_igemm_loaders.h    primitives (raw buffer loads, LDS-DMA), TileCfg, LoaderDefaults, the round-1/2 operand loaders
 //   gz_igemm_epilogues.h  epilogues of both skeletons
-//   gz_igemm_core.h       igemm_kernel (rounds 1-2), launch_igemm, split-K finish
-//   gz_igemm2.h           the igemm2 skeleton (rounds 3-5): igemm2 / igemm2w / igemm2r kernels, their loaders, launchers
+//   gz_igemm_core.h       GridMap, what the four launchers share (make_grid, launch_big_lds, the split-K finish pass),
+//                         igemm_kernel (rounds 1-2) and launch_igemm
+// the igemm2 skeleton (rounds 3-6):
+//   gz_igemm2.h           TileCfg2, ring depth / barrier interval per instantiation, LDS sizes
+//   gz_igemm2_loaders.h   the LDS-DMA loaders of igemm2_kernel
+//   gz_igemm2_kstep.h     k-step primitives (LDS reads, MFMA rows, waits), static_for, the stamp probe and GZ2_EXP_* switches
+//   gz_igemm2_kernel.h    igemm2_kernel, the KG = 2 rules, launch_igemm2
+//   gz_igemm2_wg.h        the weight-gradient kernels igemm2r / igemm2w, their loaders and launchers
 #pragma once
-#include "gz_igemm2.h"
+#include "gz_igemm2_kernel.h"
+#include "gz_igemm2_wg.h"
 
 namespace gz {
 
@@ -43,7 +50,7 @@ using Cfg128x64 = TileCfg<2, 2, 2, 1>;
 using Cfg128x32 = TileCfg<4, 1, 1, 1>;
 using Cfg64x64 = TileCfg<2, 2, 1, 1>;
 
-// round 3 (igemm2, gz_igemm2.h): one wavefront per SIMD, 128x128 / 128x64 accumulators per wavefront
+// round 3 (igemm2, gz_igemm2_kernel.h): one wavefront per SIMD, 128x128 / 128x64 accumulators per wavefront
 using Cfg256x256 = TileCfg2<2, 2, 4, 1>;
 using Cfg256x128 = TileCfg2<2, 2, 2, 2>;
 using Cfg512x64 = TileCfg2<4, 1, 2, 2>;       // 64 output channels in all (D.block1-size input gradients)

@@ -1,5 +1,10 @@
 // Part of the fp32 implicit-GEMM core (see gz_igemm.h): the round-1/2 kernel (four co-resident workgroups per CU,
-// register-staged loaders, two LDS buffers), its launcher and the split-K finish kernels.
+// register-staged loaders, two LDS buffers), the split-K finish kernels, and the host side every launcher of both
+// skeletons shares (make_grid, launch_big_lds, launch_splitk_finish) with launch_igemm.
+// The workgroup decode at the top of igemm_kernel is repeated in igemm2_kernel / igemm2r_kernel / igemm2w_kernel (the
+// latter two without phases): moved into a shared always-inline function -- like the accumulator zero and the lane
+// coordinates -- it changed instruction order and register counts of every instantiation (the helper is inlined only
+// after the early per-function passes have run), so the text stays in the kernels.
 #pragma once
 #include "gz_igemm_epilogues.h"
 
@@ -68,21 +73,6 @@ __device__ __forceinline__ void store_slab(const GridMap& gm, f32x16 (&acc)[TM][
 #define GZ_IGEMM_WAVES_PER_SIMD 4
 #endif
 
-template <class T, class = void>
-struct is_fwdrows : std::false_type {};
-template <class T>
-struct is_fwdrows<T, std::void_t<decltype(T::FWDROWS)>> : std::true_type {};
-template <class T, class = void>
-struct is_rowshare : std::false_type {};
-template <class T>
-struct is_rowshare<T, std::void_t<decltype(T::ROWSHARE)>> : std::true_type {};
-// (round 6) a row-shared loader whose reduction has a SECOND part of plain chunks (ConvDg5A2: the third horizontal tap of
-// the 5x5 s2 p2 transposed convolution's even columns), see igemm2_kernel
-template <class T, class = void>
-struct is_dualmode : std::false_type {};
-template <class T>
-struct is_dualmode<T, std::void_t<decltype(T::DUALMODE)>> : std::true_type {};
-
 template <class Cfg, class AL, class BL, class Epi>
 __global__ __launch_bounds__(NT, GZ_IGEMM_WAVES_PER_SIMD) void igemm_kernel(typename AL::Params pa, typename BL::Params pb,
                                                    typename Epi::Params pe, GridMap gm) {
@@ -91,7 +81,7 @@ __global__ __launch_bounds__(NT, GZ_IGEMM_WAVES_PER_SIMD) void igemm_kernel(type
     __shared__ __attribute__((aligned(16))) float smem[2 * BK * (LDA + LDB)];
     // row-shared A images are read one column to the left / right of the tile: keep them behind the B images so that
     // such a (masked) read stays inside this workgroup's allocation
-    constexpr bool RS0 = is_rowshare<AL>::value || is_fwdrows<AL>::value;
+    constexpr bool RS0 = AL::ROWSHARE || AL::FWDROWS;
     float* As = RS0 ? smem + 2 * BK * LDB : smem;
     float* Bs = RS0 ? smem : smem + 2 * BK * LDA;
 
@@ -143,7 +133,7 @@ __global__ __launch_bounds__(NT, GZ_IGEMM_WAVES_PER_SIMD) void igemm_kernel(type
     const int lane = tid & 63, wave = tid >> 6;
     const int wm = wave / Cfg::WN, wn = wave % Cfg::WN;
     const int half = lane >> 5, l32 = lane & 31;
-    constexpr bool RS = is_rowshare<AL>::value;       // ConvDgALoaderRow4: one LDS row per k-step, taps applied on read
+    constexpr bool RS = AL::ROWSHARE;       // ConvDgALoaderRow4: one LDS row per k-step, taps applied on read
     int a_rd = half * LDA + wm * TM * 32 + l32;
     constexpr int A_STEP = RS ? LDA : 2 * LDA;
     bool a_zero[TM];
@@ -156,7 +146,7 @@ __global__ __launch_bounds__(NT, GZ_IGEMM_WAVES_PER_SIMD) void igemm_kernel(type
             a_zero[i] = (sh < 0 && b == 0) || (sh > 0 && b == pa.AW - 1);
         }
     }
-    constexpr bool FR = is_fwdrows<AL>::value;        // ConvFwdALoaderRow4: raw input rows, taps applied on read
+    constexpr bool FR = AL::FWDROWS;        // ConvFwdALoaderRow4: raw input rows, taps applied on read
     int fr_base[TM];
     bool fr_ze[TM], fr_zo[TM];
     int fr_2ow = 0;
@@ -375,16 +365,19 @@ inline int split_nz(int K, int splits) {
     return nz < 1 ? 1 : nz;
 }
 
-// `slab` != null: split-K through raw-accumulator slabs + splitk_finish_kernel<Epi> (needs
-// ny * split_nz(K, splits) * M * N floats); null with splits > 1: the epilogue itself is slab-aware (Wg).
-template <class Cfg, class AL, class BL, class Epi>
-inline int launch_igemm(const typename AL::Params& pa, const typename BL::Params& pb,
-                        const typename Epi::Params& pe, int M, int N, int K, int ny, int splits,
-                        hipStream_t stream, float* slab = nullptr, const int* phase_chunks = nullptr) {
+// The GridMap of a launch -- and, for a split launch with phases of unequal length, its SlabMap -- with the grid.
+// `slab` != null: split-K through raw-accumulator slabs + splitk_finish_kernel<Epi> (needs ny * split_nz(K, splits) * M * N
+// floats); null with splits > 1: the epilogue itself is slab-aware (Wg).  `phase_chunks`: chunks per phase (ny <= 8).
+struct GridPlan {
     GridMap gm;
+    SlabMap sm;
+    int nz;
+    dim3 grid;
+};
+inline GridPlan make_grid(int BM, int BN, int M, int N, int K, int ny, int splits, float* slab, const int* phase_chunks) {
+    GridPlan g{};
+    GridMap& gm = g.gm;
     gm.no_swizzle = knobs().no_xcd_swizzle;
-    gm.stagger = 0;
-    gm.var_chunks = 0;
     if (phase_chunks && ny <= 8) {
         gm.var_chunks = 1;
         for (int i = 0; i < ny; ++i) {
@@ -398,46 +391,73 @@ inline int launch_igemm(const typename AL::Params& pa, const typename BL::Params
                 gm.phase_order[j - 1] = t;
             }
     }
-    gm.slab = nullptr;
     gm.slab_m = M;
     gm.slab_n = N;
-    gm.tiles_m = (M + Cfg::BM - 1) / Cfg::BM;
-    gm.tiles_n = (N + Cfg::BN - 1) / Cfg::BN;
+    gm.tiles_m = (M + BM - 1) / BM;
+    gm.tiles_n = (N + BN - 1) / BN;
     gm.chunks = (K + BK - 1) / BK;
     if (splits < 1) splits = 1;
     gm.chunks_per_split = (gm.chunks + splits - 1) / splits;
-    int nz = (gm.chunks + gm.chunks_per_split - 1) / gm.chunks_per_split;
-    if (nz < 1) nz = 1;
+    g.nz = (gm.chunks + gm.chunks_per_split - 1) / gm.chunks_per_split;
+    if (g.nz < 1) g.nz = 1;
     gm.ny = ny;
-    dim3 grid(gm.tiles_m * gm.tiles_n * ny, 1, nz);
-    if (slab && nz > 1) gm.slab = slab;
-    SlabMap sm;
-    sm.var = gm.slab && gm.var_chunks;
+    g.grid = dim3(gm.tiles_m * gm.tiles_n * ny, 1, g.nz);
+    if (slab && g.nz > 1) gm.slab = slab;
+    g.sm.var = gm.slab && gm.var_chunks;
     for (int i = 0, at = 0; i < 8; ++i) {
-        int n = (sm.var && i < ny) ? (gm.phase_chunks[i] + gm.chunks_per_split - 1) / gm.chunks_per_split : 0;
-        gm.phase_nz[i] = sm.nz[i] = n;
-        gm.phase_slab0[i] = sm.slab0[i] = at;
+        int n = (g.sm.var && i < ny) ? (gm.phase_chunks[i] + gm.chunks_per_split - 1) / gm.chunks_per_split : 0;
+        gm.phase_nz[i] = g.sm.nz[i] = n;
+        gm.phase_slab0[i] = g.sm.slab0[i] = at;
         at += n;
     }
+    return g;
+}
+
+// Launch of a kernel with dynamic LDS above the default limit: hipFuncAttributeMaxDynamicSharedMemorySize is set on the
+// first use of the instantiation (one flag per KERN).  False: the attribute could not be set, nothing was launched.
+template <auto KERN, class... Args>
+inline bool launch_big_lds(dim3 grid, int threads, size_t lds, hipStream_t stream, const Args&... args) {
+    static bool attr_done = false;
+    if (!attr_done) {
+        if (hipFuncSetAttribute((const void*)KERN, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+            return false;
+        attr_done = true;
+    }
+    hipLaunchKernelGGL(KERN, grid, dim3(threads), lds, stream, args...);
+    return true;
+}
+
+// second pass of a split launch through slabs (g.gm.slab != null)
+template <class Epi>
+inline void launch_splitk_finish(const GridPlan& g, int M, int N, int ny, const typename Epi::Params& pe, hipStream_t stream) {
+    const int fm = (M + 31) / 32, fn = (N + 31) / 32;
+    // many slabs over few output blocks: 8 wavefronts share the slab walk
+    if (g.nz > 16)
+        hipLaunchKernelGGL((splitk_finish_kernel<Epi, 8>), dim3(fm * fn * ny), dim3(512), 0, stream, g.gm.slab, g.nz, M, N,
+                           pe, fn, ny, g.sm);
+    else
+        hipLaunchKernelGGL((splitk_finish_kernel<Epi, 4>), dim3(fm * fn * ny), dim3(NT), 0, stream, g.gm.slab, g.nz, M, N,
+                           pe, fn, ny, g.sm);
+}
+
+// same contract as make_grid
+template <class Cfg, class AL, class BL, class Epi>
+inline int launch_igemm(const typename AL::Params& pa, const typename BL::Params& pb,
+                        const typename Epi::Params& pe, int M, int N, int K, int ny, int splits,
+                        hipStream_t stream, float* slab = nullptr, const int* phase_chunks = nullptr) {
+    const GridPlan g = make_grid(Cfg::BM, Cfg::BN, M, N, K, ny, splits, slab, phase_chunks);
     const int dyn_lds = knobs().dyn_lds;   // experiment: throttle workgroups per CU
-    hipLaunchKernelGGL((igemm_kernel<Cfg, AL, BL, Epi>), grid, dim3(NT), dyn_lds, stream, pa, pb, pe, gm);
-    if (gm.slab) {
-        const int fm = (M + 31) / 32, fn = (N + 31) / 32;
+    hipLaunchKernelGGL((igemm_kernel<Cfg, AL, BL, Epi>), g.grid, dim3(NT), dyn_lds, stream, pa, pb, pe, g.gm);
+    if (g.gm.slab) {
         if constexpr (std::is_same<Epi, EpiRowMajor>::value) {
-            if (nz > 8) {
+            if (g.nz > 8) {
                 const long long total = (long long)M * N * ny;
                 hipLaunchKernelGGL(splitk_finish_rowmajor_kernel<4>, dim3((unsigned)((total + 63) / 64)), dim3(256), 0, stream,
-                                   slab, nz, pe, ny);
+                                   slab, g.nz, pe, ny);
                 return launch_status();
             }
         }
-        // many slabs over few output blocks: 8 wavefronts share the slab walk
-        if (nz > 16)
-            hipLaunchKernelGGL((splitk_finish_kernel<Epi, 8>), dim3(fm * fn * ny), dim3(512), 0, stream, slab, nz, M, N,
-                               pe, fn, ny, sm);
-        else
-            hipLaunchKernelGGL((splitk_finish_kernel<Epi, 4>), dim3(fm * fn * ny), dim3(NT), 0, stream, slab, nz, M, N, pe,
-                               fn, ny, sm);
+        launch_splitk_finish<Epi>(g, M, N, ny, pe, stream);
     }
     return launch_status();
 }

@@ -37,13 +37,36 @@ struct TileCfg {
     static_assert(WM * WN == 4, "4 wavefronts per workgroup");
 };
 
+// What a kernel may ask of an operand loader, with the answer of a loader that says nothing.  Every loader inherits
+// this and shadows what it answers differently; the kernels read AL::NAME (igemm_kernel: ROWSHARE, FWDROWS).
+struct LoaderDefaults {
+    static constexpr bool ROWSHARE = false;      // one LDS row per k-step, the horizontal tap applied on the fragment read
+    static constexpr bool FWDROWS = false;       // raw input rows, taps applied on the fragment read
+    static constexpr bool TAPGATHER = false;     // a tap-major gather whose launches also build the KG = 2 kernel
+    static constexpr bool PADSKIP = false;       // 4x4 maps staged (row, image, column): padding-only blocks left out
+    static constexpr int EXTRA = 0;              // zeroed floats behind the A image of a stage
+    static constexpr int OW_C = 1;               // FWDROWS: output columns per row (the row step is an immediate)
+    // multi-mode loaders (ConvDg5A2): a row-shared reduction with a second part of plain chunks
+    static constexpr bool DUALMODE = false;
+    static constexpr int MODES = 1;
+    static constexpr int KSTEPS = BK / 2;        // k-steps per chunk
+    static constexpr bool step_plain(int m, int S) { return false; }     // k-step S of a mode-m chunk: plain or row-shared
+    static constexpr unsigned step_mask(int m, int S) { return 0xFu; }   // ... the accumulator blocks its MFMAs feed
+    static constexpr int step_arow(int m, int S) { return S; }           // ... its first LDS row (plain: two rows per step)
+    static constexpr int step_brow(int m, int S) { return 2 * S; }       // ... the first row of the B image it multiplies
+    // pad-skip loaders: the accumulator blocks (bit i = block i of the wavefront) whose rows are all padding at k-step S
+    // of a chunk in skip mode m, and "block 0 in the k-steps of one parity, known at launch time"
+    static constexpr unsigned skip_mask(int m, int S) { return 0u; }
+    static constexpr bool SKIP_BLOCK0_BY_PARITY = false;
+};
+
 // ---------------------------------------------------------------------------
 // generic matrix loaders
 // ---------------------------------------------------------------------------
 
 // element (k, mn) at base[k*ld + mn]; mn contiguous; scalar loads.
 template <int BMN>
-struct MContigLoader {
+struct MContigLoader : LoaderDefaults {
     struct Params {
         const float* base;
         int K, MN, ld;
@@ -100,7 +123,7 @@ struct MContigLoader {
 
 // same layout, 16-byte loads; requires ld % 4 == 0, MN % 4 == 0 and a 16-byte aligned base.
 template <int BMN>
-struct MContigLoader4 {
+struct MContigLoader4 : LoaderDefaults {
     using Params = typename MContigLoader<BMN>::Params;
     static constexpr int LD = BMN;
     static constexpr int C4 = BMN / 4;                 // float4 columns
@@ -174,7 +197,7 @@ struct MContigLoader4 {
 // LD = BMN + 2 makes the transposing ds_write_b32 conflict-free: a half-wave
 // holds 16 k x 2 mn and lands on banks (2k + mn) mod 32.
 template <int BMN>
-struct KContigLoader {
+struct KContigLoader : LoaderDefaults {
     struct Params {
         const float* base;
         int K, MN, ld;
@@ -217,7 +240,7 @@ struct KContigLoader {
 // ---------------------------------------------------------------------------
 // A operand of the forward GEMM: A[m = (n, oy, ox)][k = (c, ky, kx)] = x[n][c][oy*S-P+ky][ox*S-P+kx]
 template <int BM, int KH, int KW, int S, int P>
-struct ConvFwdALoader {
+struct ConvFwdALoader : LoaderDefaults {
     struct Params {
         const float* x;
         ConvShape s;
@@ -308,7 +331,7 @@ struct ConvFwdALoader {
 // load from column 0 and rotate the vector by one in registers: nothing is ever read in front of the
 // tensor (an address before a page-aligned allocation faults even if the value is discarded).
 template <int BM, int S, int P>
-struct ConvFwdALoaderK4V {
+struct ConvFwdALoaderK4V : LoaderDefaults {
     using Params = typename ConvFwdALoader<BM, 4, 4, S, P>::Params;
     static constexpr int LD = BM;
     static constexpr int NPARTS = 0;
@@ -377,7 +400,7 @@ struct ConvFwdALoaderK4V {
 // of the image (ox = 0, kx = 0) and right of it (ox = OW-1, kx = 3) are zeroed in the register; rows above / below
 // are dropped by the descriptor's range check.  Needs W = 2*OW, H = 2*OH, OW <= BM, BM % OW == 0, 16-byte alignment.
 template <int BM>
-struct ConvFwdALoaderRow4 {
+struct ConvFwdALoaderRow4 : LoaderDefaults {
     using Params = typename ConvFwdALoader<BM, 4, 4, 2, 1>::Params;
     static constexpr int LD = BM;
     static constexpr bool DMA = true;
@@ -426,7 +449,7 @@ struct ConvFwdALoaderRow4 {
 // (taps with ky >= KH are zero in the packed weights).  Per phase:
 //   A[m = (n, a, b)][k = (ko, ty, tx)] = y[n][ko][a + dy(ty)][b + dx(tx)]
 template <int BM, int KH, int KW, int S, int P>
-struct ConvDgALoader {
+struct ConvDgALoader : LoaderDefaults {
     static constexpr int TY = (KH + S - 1) / S, TX = (KW + S - 1) / S;
     static constexpr int TAPS = TY * TX;
     struct Params {
@@ -547,7 +570,7 @@ struct ConvDgALoader {
 // from the neighbouring image row (b = 0 for -1, b = AW - 1 for +1) is zeroed in the register (a lane's b is fixed).
 // Half the LDS-DMA bytes, an eighth of the instructions.  Needs AW % 4 == 0 and a 16-byte aligned tensor.
 template <int BM, int KH, int KW, int S, int P>
-struct ConvDgALoaderRow4 {
+struct ConvDgALoaderRow4 : LoaderDefaults {
     static_assert(KH == 4 && KW == 4 && S == 2 && P == 1, "k4 s2 p1 only");
     static constexpr int TAPS = 4;
     static constexpr bool UNIFORM = true, FIXED = true;
@@ -598,7 +621,7 @@ struct ConvDgALoaderRow4 {
 // Weight gradient: dW[ko][(c, ky, kx)] = sum_{p = (n, oy, ox)} y[n][ko][oy][ox] * x[n][c][oy*S-P+ky][ox*S-P+kx]
 // A[m = ko][k = p] : k-contiguous inside one image.
 template <int BM>
-struct WgALoader {
+struct WgALoader : LoaderDefaults {
     struct Params {
         const float* y;
         ConvShape s;
@@ -651,7 +674,7 @@ struct WgALoader {
 
 // B[k = p][n = (c, ky, kx)] = x[n_img][c][oy*S-P+ky][ox*S-P+kx]
 template <int BN, int KH, int KW, int S, int P>
-struct WgBLoader {
+struct WgBLoader : LoaderDefaults {
     struct Params {
         const float* x;
         ConvShape s;
@@ -725,7 +748,7 @@ struct WgRowGeom {
 };
 
 template <int BM>
-struct WgALoaderRow {
+struct WgALoaderRow : LoaderDefaults {
     struct Params {
         const float* y;
         ConvShape s;
@@ -773,7 +796,7 @@ struct WgALoaderRow {
 };
 
 template <int BN, int KH, int KW, int S, int P>
-struct WgBLoaderRow {
+struct WgBLoaderRow : LoaderDefaults {
     struct Params {
         const float* x;
         ConvShape s;
@@ -851,7 +874,7 @@ struct Conv3DShape {
 
 // forward 3-D conv: A[m = (n, od, oy, ox)][k = (c, kd, ky, kx)]
 template <int BM, int KS, int S, int P>
-struct Conv3DFwdALoader {
+struct Conv3DFwdALoader : LoaderDefaults {
     struct Params {
         const float* x;
         Conv3DShape s;
@@ -909,7 +932,7 @@ struct Conv3DFwdALoader {
 
 // transposed 3-D conv, phase (pd, py, px): A[m = (n, a, b, c)][k = (ko, td, ty, tx)]
 template <int BM, int KS, int S, int P>
-struct Conv3DDgALoader {
+struct Conv3DDgALoader : LoaderDefaults {
     static constexpr int T = (KS + S - 1) / S;
     static constexpr int TAPS = T * T * T;
     struct Params {
@@ -979,7 +1002,7 @@ struct Conv3DDgALoader {
 
 // 3-D weight gradient, B[k = p = (n, od, oy, ox)][col = (c, kd, ky, kx)]
 template <int BN, int KS, int S, int P>
-struct Wg3DBLoader {
+struct Wg3DBLoader : LoaderDefaults {
     struct Params {
         const float* x;
         Conv3DShape s;
@@ -1079,7 +1102,7 @@ struct Wg3DBLoader {
 //   tap_bytes(tap)       the tap's scalar byte offset
 //   inside(pix, tap)     does the tap of this pixel lie in the tensor
 // TAPGATHER marks the geometries whose igemm2 launches also build the two-wave-group kernel (igemm2_kg2_built).
-// The staging bodies are TapGatherLoader below (four waves per tile, igemm_kernel) and TapGatherA2 (gz_igemm2.h).
+// The staging bodies are TapGatherLoader below (four waves per tile, igemm_kernel) and TapGatherA2 (gz_igemm2_loaders.h).
 // ---------------------------------------------------------------------------
 constexpr int PAST_M = -(1 << 20);
 struct Pix2 { int y, x; };
@@ -1208,6 +1231,7 @@ struct TapGeoDg {
 template <int BM_, int KS, int S, int P>
 struct TapGeoFwd3D {
     static constexpr int BM = BM_;
+    static constexpr bool TAPGATHER = false;
     using Params = typename Conv3DFwdALoader<BM, KS, S, P>::Params;
     using Pix = Pix3;
     int chans, plane, D, H, W;
@@ -1245,6 +1269,7 @@ struct TapGeoFwd3D {
 template <int BM_, int KS, int S, int P>
 struct TapGeoDg3D {
     static constexpr int BM = BM_;
+    static constexpr bool TAPGATHER = false;
     static constexpr int T = (KS + S - 1) / S;
     using Params = typename Conv3DDgALoader<BM, KS, S, P>::Params;
     using Pix = Pix3;
@@ -1286,7 +1311,7 @@ struct TapGeoDg3D {
 // The four-wave staging body (igemm_kernel): thread (m_l, kb) owns pixel m_l and the EPT channel rows kb + STEP * j
 // of every chunk; its voffsets are loop-invariant, a chunk costs one tap decode and one inside() test.
 template <class Geo_>
-struct TapGatherLoader {
+struct TapGatherLoader : LoaderDefaults {
     using Geo = Geo_;
     using Params = typename Geo::Params;
     static constexpr int BM = Geo::BM, LD = BM;

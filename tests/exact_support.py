@@ -119,6 +119,41 @@ def split_count(text):
     return max([int(v) for v in re.findall(r"(?:splits|slabs)=(\d+)", text)], default=0)
 
 
+def launch_path(text, op, phases):
+    """(launcher, path) a plan text stands for, in the terms of csrc/gz_igemm_core.h make_grid: which of launch_igemm /
+    launch_igemm2 / launch_igemm2r / launch_igemm2w, unsplit or how the split reduction is finished (the weight
+    gradient's epilogue writes its own slabs; the others go through raw slabs and splitk_finish_kernel<Epi, 8> above 16
+    slabs, <Epi, 4> up to 16), ``phases`` = the launch passes per-phase chunk counts (GridMap::var_chunks), and the
+    two-wave-group kernel.  None: a direct kernel."""
+    m = re.search(r"\b(igemm2w|igemm2r|igemm2|igemm)<", text)
+    if not m:
+        return None
+    n = split_count(text) or 1
+    if n == 1:
+        path = "unsplit"
+    elif op == "Wg":
+        path = "split: epilogue slabs"
+    else:
+        path = "split: finish<8>" if n > 16 else "split: finish<4>"
+    return m.group(1), ("phases " if phases else "") + ("KG=2 " if "wave_groups=2" in text else "") + path
+
+
+def launch_paths():
+    """{(launcher, path): [test ids]} over the conv2d and conv3d case tables (host only).  Per-phase chunk counts: the 2-D
+    input gradients of the tap-major loaders at stride 2 with other than 4x4 taps (run_dgrad*: 9 / 6 / 6 / 4 taps per
+    phase at 5x5), every 3-D input gradient."""
+    out = {}
+    for c, op, form, split in CONV_ROWS:
+        text = conv2d_plan(op, *c)
+        phases = op == "Dg" and c.s == 2 and c.k != 4 and "Tap" in text
+        out.setdefault(launch_path(text, op, phases), []).append("test_conv2d_at_every_plan_form[%s]" % row_id((c, op)))
+    for c, op, form in CONV3_ROWS:
+        text = conv3d_plan(op, *c)
+        out.setdefault(launch_path(text, op, op == "Dg"), []).append("test_conv3d_family[%s]" % row3_id((c, op)))
+    out.pop(None, None)
+    return out
+
+
 ENUM_NS = [1, 2, 3, 4, 8, 16, 32, 33, 50, 64, 128, 131, 256, 512]
 ENUM_CS = [1, 2, 3, 4, 6, 16, 20, 32, 64, 72, 128, 132, 256, 384, 512, 1024]
 ENUM_HS = [4, 8, 12, 16, 24, 32, 64]
@@ -390,6 +425,9 @@ _CONV_TABLE = [
     ((37, 256, 16, 1024, 5, 2, 2), 'Dg', 'Dg igemm2<256x(4 phases x 32)> ConvDg5A2(row-shared, LDS-DMA 16B, 12 k-steps) slabs= (no bias / activation, aligned tensors; else the gather loader)', True),
     ((37, 1024, 16, 256, 5, 2, 2), 'Dg', 'Dg igemm2<256x(4 phases x 32)> ConvDg5A2(row-shared, LDS-DMA 16B, 12 k-steps) slabs= (no bias / activation, aligned tensors; else the gather loader)', False),
     ((2, 1056, 64, 256, 5, 2, 2), 'Dg', 'Dg igemm2<256x(4 phases x 32)> ConvDg5A2(row-shared, LDS-DMA 16B, 12 k-steps) slabs= (no bias / activation, aligned tensors; else the gather loader)', False),
+    # launch_igemm2 with more than 16 slabs (22: the eight-wavefront finish pass), one wave group, equal phases -- the one
+    # path of launch_paths() that only the wave_groups=2 and the per-phase launches above reached
+    ((33, 512, 8, 256, 5, 2, 2), 'F', 'F igemm2<256x64> ConvTapA2(gather, LDS-DMA 4B) slabs= bn_stats_rows=', True),
 ]
 CONV_ROWS = [(ConvCase(*sh), op, form, split) for sh, op, form, split in _CONV_TABLE]
 

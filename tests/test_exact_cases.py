@@ -163,6 +163,23 @@ def test_split_and_unsplit_launches_are_what_the_table_says():
         assert (S.split_count(S.conv2d_plan(op, *c)) > 1) == split, (c, op)
 
 
+# every path through the four launchers' shared host code (make_grid, launch_big_lds, launch_splitk_finish) that a
+# launcher has: the arithmetic a comparison of device code does not see
+LAUNCH_PATHS = [(L, p) for L in ("igemm", "igemm2") for p in
+                ("unsplit", "split: finish<4>", "split: finish<8>", "split: epilogue slabs", "phases unsplit",
+                 "phases split: finish<4>", "phases split: finish<8>")]
+LAUNCH_PATHS.remove(("igemm2", "split: epilogue slabs"))      # (its weight gradients are igemm2w / igemm2r)
+LAUNCH_PATHS += [("igemm2", "KG=2 unsplit"), ("igemm2", "KG=2 split: finish<4>"), ("igemm2", "KG=2 split: finish<8>"),
+                 ("igemm2r", "unsplit"), ("igemm2r", "split: epilogue slabs"),
+                 ("igemm2w", "unsplit"), ("igemm2w", "split: epilogue slabs")]
+
+
+def test_every_path_through_the_launchers_has_a_case():
+    have = S.launch_paths()
+    missing = [k for k in LAUNCH_PATHS if not have.get(k)]
+    assert not missing, "launcher paths without an exact case: %s" % missing
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # sensitivity: what a subtly wrong kernel would return is NOT equal -- one case per direction and the GEMM
 # ---------------------------------------------------------------------------------------------------------------------

@@ -1,4 +1,4 @@
-"""The pad-skip forms of igemm2's k4 s2 p1 row loaders on 4x4 maps (csrc/gz_igemm2.h: ConvFwdA2<256, 4, true>,
+"""The pad-skip forms of igemm2's k4 s2 p1 row loaders on 4x4 maps (csrc/gz_igemm2_loaders.h: ConvFwdA2<256, 4, true>,
 ConvDgA2<256, true>): a wavefront's 32-row blocks are staged uniform in the map row, the (block, k-step)
 pairs whose vertical tap is padding only are not multiplied, and the accumulators go back to pixel order through LDS
 before the epilogue.

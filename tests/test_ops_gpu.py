@@ -95,7 +95,7 @@ DG5_CASES = [
 @pytest.mark.parametrize("case", DG5_CASES)
 def test_transposed_conv_5x5_row_shared_four_phases(case):
     """Round 6: the 5x5 s2 p2 input gradient on row-shared LDS rows with all four output phases per workgroup (csrc/
-    gz_igemm2.h ConvDg5A2 / DgQuadB2, EpiPhaseQuadB; HoloGAN's critic, reference core/models/hologan_discriminator.py:7-23)
+    gz_igemm2_loaders.h ConvDg5A2 / DgQuadB2, EpiPhaseQuadB; HoloGAN's critic, reference core/models/hologan_discriminator.py:7-23)
     against torch's conv_transpose2d: every row / column phase, image-edge zero columns (shift -1 at b = 0, +1 at b = AW
     - 1), top / bottom rows, ragged last tile, one to eight column tiles, both chunk modes, unsplit and split launches
     (the finish pass's single-block store path); bit-for-bit repeatable; the packed image is the tap-major one the gather

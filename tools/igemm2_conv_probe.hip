@@ -1,6 +1,6 @@
 // Timing harness for the igemm2 skeleton with the transposed-convolution loaders (no packing, random data, results
 // not checked: correctness lives in tests/test_ops_gpu.py): per-workgroup s_memtime stamps -> prologue / main loop /
-// epilogue cycles, with the shader clock warmed up.  Experiment macros of csrc/gz_igemm.h (-DGZ2_EXP_*) apply.
+// epilogue cycles, with the shader clock warmed up.  Experiment macros of csrc/gz_igemm2_kstep.h (-DGZ2_EXP_*) apply.
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -DGZ2_STAMPS -I include -I lightning_gan_zoo_amd/csrc \
 //         -o tools/bin/igemm2_conv_probe tools/igemm2_conv_probe.hip
 //   tools/bin/igemm2_conv_probe N K OH C [tile: 128|256] [lds_extra]
