@@ -636,6 +636,44 @@ size_t gz_inception_score_workspace_bytes(long long n, int classes, int splits);
 int gz_inception_score(const double* logits, long long n, int classes, int splits, double* scores,
                        void* workspace, size_t ws_bytes, hipStream_t stream);
 
+/* ---- precision / recall / density / coverage on the device (csrc/gz_prdc.hip) ---------------------------
+ * The k-nearest-neighbour manifold metrics (improved precision and recall, Kynkaanniemi et al. 2019; density and coverage,
+ * Naeem et al. 2020) of fp64 row-major DEVICE codes, on SQUARED Euclidean distances in the Gram form
+ * D(x, y) = max(0, |x|^2 + |y|^2 - 2 <x, y>) on v_mfma_f64_16x16x4_f64, without a distance matrix in memory.  All
+ * comparisons are <=.  n, n_g, n_r and d need no multiple of anything (an index outside an operand is never
+ * dereferenced); row offsets are 64-bit.
+ *
+ * gz_knn_radii: radii[i] = the k-th smallest of D(codes_i, codes_j) over j != i (self excluded by index: exact duplicates
+ * give 0) into n DEVICE doubles, 1 <= k <= 8, k < n.  Selection by value: the same bits for every slicing of the walk.
+ * Three launches on `stream`.
+ *
+ * gz_prdc_counts: one walk over the n_g x n_r cross distances, each tile computed once, with rad_g [n_g] and rad_r [n_r]
+ * (gz_knn_radii's, or any DEVICE doubles):
+ *     in_real[j] = #{i : D(G_j, R_i) <= rad_r[i]}   int32 [n_g]        in_fake[i] = #{j : D(G_j, R_i) <= rad_g[j]}   int32 [n_r]
+ *     near[i]    = min_j D(G_j, R_i)                double [n_r]
+ *     totals     = #{in_real > 0}, #{in_fake > 0}, sum in_real, #{near <= rad_r}                     int64 [4]
+ * so that precision = totals[0] / n_g, recall = totals[1] / n_r, density = totals[2] / (k n_g), coverage = totals[3] / n_r.
+ * Five launches on `stream`.
+ *
+ * gz_prdc_plan: the grid gz_prdc_counts takes for n_rows generated and n_cols real rows at the current CU budget
+ * (gz_set_cu_budget): row_groups groups of row tiles (at most 128, equal up to one tile) times col_slices slices of column
+ * tiles (as many as fit with them into one round of two workgroups per CU, at most one per column tile).  It depends on
+ * nothing else.  gz_knn_radii of n rows takes the plan of (n, n).
+ *
+ * Deterministic: no atomics, every count an integer sum and near a minimum, and neither the outputs nor the workspaces
+ * (gz_knn_radii_workspace_bytes / gz_prdc_counts_workspace_bytes bytes) have to be zeroed; two calls give equal bits.
+ * GZ_ERR_BAD_SHAPE: k < 1, k > 8, k >= n, n_g, n_r or d below 1, a null pointer; GZ_ERR_TOO_LARGE: a grid beyond 2^31 - 1
+ * workgroups or an array beyond the address space; GZ_ERR_WORKSPACE: workspace too short (nothing is launched; the size
+ * queries return 0 for a refused shape). */
+size_t gz_knn_radii_workspace_bytes(long long n, int d, int k);
+int gz_knn_radii(const double* codes, long long n, int d, int k, double* radii, void* workspace, size_t ws_bytes,
+                 hipStream_t stream);
+size_t gz_prdc_counts_workspace_bytes(long long n_g, long long n_r, int d);
+int gz_prdc_counts(const double* codes_g, long long n_g, const double* rad_g, const double* codes_r, long long n_r,
+                   const double* rad_r, int d, int* in_real, int* in_fake, double* near, long long* totals,
+                   void* workspace, size_t ws_bytes, hipStream_t stream);
+int gz_prdc_plan(long long n_rows, long long n_cols, int* row_groups, int* col_slices);
+
 /* text of the last HIP error seen by a launcher on the calling thread ("" if none) */
 const char* gz_last_error(void);
 

@@ -22,6 +22,8 @@ csrc/gz_moments.hip) and KID's sums.  The matrix square root stays on the host u
 alone, on the fp64 MFMA product of csrc/gz_sqrtm.hip.  ``frechet_distance_newton_schulz`` is the same recurrence in numpy.
 With ``classifier=`` it also reports the Inception Score (gan_stability's metrics/inception_score.py) of the resident
 codes: ``inception_score_device`` on csrc/gz_inception_score.hip, ``inception_score_from_logits`` its host yardstick.
+With ``prdc_k=`` it reports improved precision / recall and density / coverage of the two resident code sets as well:
+``prdc_device`` on csrc/gz_prdc.hip, ``prdc`` its host yardstick (the reference has neither).
 """
 import numpy as np
 import torch
@@ -507,6 +509,136 @@ def inception_score_device(codes, weight, bias=None, splits=10):
     return float(np.mean(split_scores)), float(np.std(split_scores)), split_scores
 
 
+PRDC_MAX_K = 8          # the device kernels keep a row's k smallest distances in registers (csrc/gz_prdc.hip)
+
+
+def _prdc_check(k, *sets):
+    k = int(k)
+    d = None
+    for codes in sets:
+        if codes.ndim != 2 or codes.shape[1] < 1 or (d is not None and codes.shape[1] != d):
+            raise ValueError("codes must be [n, d] arrays of one d >= 1, got %s" % (tuple(codes.shape),))
+        d = codes.shape[1]
+    if k < 1 or k > PRDC_MAX_K or k >= min(c.shape[0] for c in sets):
+        raise ValueError("k must lie in 1 .. %d and below the smaller set's %d rows, got %d"
+                         % (PRDC_MAX_K, min(c.shape[0] for c in sets), k))
+    return k
+
+
+def _sq_distances(x, y):
+    """Squared Euclidean distances [len(x), len(y)] from direct differences, ``((x_i - y_j) ** 2).sum()``."""
+    return ((x[:, None, :] - y[None, :, :]) ** 2).sum(axis=2)
+
+
+def _row_blocks(n, n_other, d, budget=1 << 21):
+    """Row ranges whose [rows, n_other, d] difference block stays under ``budget`` doubles."""
+    step = max(1, int(budget // max(1, n_other * d)))
+    return [(a, min(n, a + step)) for a in range(0, n, step)]
+
+
+def knn_radii(codes, k):
+    """``rad[i]``: the k-th smallest SQUARED distance from row i to the other rows of ``codes`` [n, d], self excluded by
+    index (exact duplicates give 0).  Numpy fp64 on direct differences, blocked over rows.  The yardstick of
+    ``knn_radii_device``."""
+    codes = np.asarray(codes, dtype=np.float64)
+    k = _prdc_check(k, codes)
+    n, d = codes.shape
+    rad = np.empty(n)
+    for a, b in _row_blocks(n, n, d):
+        dist = _sq_distances(codes[a:b], codes)
+        dist[np.arange(b - a), np.arange(a, b)] = np.inf
+        rad[a:b] = np.partition(dist, k - 1, axis=1)[:, k - 1]
+    return rad
+
+
+def prdc(codes_g, codes_r, k=5):
+    """Improved precision and recall (Kynkaanniemi et al. 2019) and density and coverage (Naeem et al. 2020) of generated
+    codes ``codes_g`` [n_g, d] against real codes ``codes_r`` [n_r, d] on the host: numpy fp64 on SQUARED distances from
+    direct differences (deliberately not the Gram form the device uses), blocked over rows.  With ``rad_X[i]`` the k-th
+    smallest distance from row i of X to the other rows of X (``knn_radii``):
+
+        in_real[j] = #{i : D(G_j, R_i) <= rad_R[i]}      in_fake[i] = #{j : D(G_j, R_i) <= rad_G[j]}
+        near[i]    = min_j D(G_j, R_i)
+        precision  = #{in_real > 0} / n_g                recall   = #{in_fake > 0} / n_r
+        density    = sum in_real / (k n_g)               coverage = #{near <= rad_R} / n_r
+
+    Every comparison is ``<=``, as in the improved precision and recall paper.  The ``prdc`` package of the density and
+    coverage paper is remembered to compare with a strict ``<``, which differs on exact ties only; neither package was
+    at hand to check, so that is a recollection, not a verified fact.  ``k`` = 5 is the density and coverage paper's
+    value (Kynkaanniemi et al. use 3).  -> dict of the four floats, the per-row arrays ``in_real`` [n_g], ``in_fake``
+    [n_r], ``near`` [n_r] and the radii ``rad_g``, ``rad_r``.  The yardstick ``prdc_device`` is measured against."""
+    g, r = np.asarray(codes_g, dtype=np.float64), np.asarray(codes_r, dtype=np.float64)
+    k = _prdc_check(k, g, r)
+    (n_g, d), n_r = g.shape, r.shape[0]
+    rad_g, rad_r = knn_radii(g, k), knn_radii(r, k)
+    in_real = np.empty(n_g, dtype=np.int64)
+    in_fake = np.zeros(n_r, dtype=np.int64)
+    near = np.full(n_r, np.inf)
+    for a, b in _row_blocks(n_g, n_r, d):
+        dist = _sq_distances(g[a:b], r)
+        in_real[a:b] = (dist <= rad_r[None, :]).sum(axis=1)
+        in_fake += (dist <= rad_g[a:b, None]).sum(axis=0)
+        near = np.minimum(near, dist.min(axis=0))
+    return {"precision": float((in_real > 0).sum() / n_g), "recall": float((in_fake > 0).sum() / n_r),
+            "density": float(in_real.sum() / (k * n_g)), "coverage": float((near <= rad_r).sum() / n_r),
+            "in_real": in_real, "in_fake": in_fake, "near": near, "rad_g": rad_g, "rad_r": rad_r}
+
+
+def knn_radii_device(codes, k):
+    """``knn_radii`` of fp64 device codes [n, d] as an fp64 device tensor [n]: gz_knn_radii (csrc/gz_prdc.hip), squared
+    distances in the Gram form on the fp64 MFMA tile core.  Bit-deterministic.  No CPU fallback."""
+    from . import functional as F
+    from ._lib import check, lib
+    codes = _fp64_device_codes(codes, "k-nearest-neighbour radii", "eval.knn_radii")
+    k = _prdc_check(k, codes)
+    n, d = codes.shape
+    with torch.cuda.device(codes.device):
+        radii = torch.empty((n,), dtype=torch.float64, device=codes.device)
+        ws_bytes = lib.gz_knn_radii_workspace_bytes(n, d, k)
+        ws = torch.empty(max(ws_bytes, 8), dtype=torch.uint8, device=codes.device)
+        check(lib.gz_knn_radii(F._p(codes), n, d, k, F._p(radii), F._p(ws), ws_bytes, F._stream()), "knn_radii")
+    return radii
+
+
+def prdc_device(codes_g, codes_r, k=5, rad_r=None, rad_g=None):
+    """``prdc`` on fp64 device codes: two gz_knn_radii calls and one gz_prdc_counts walk over the cross distances
+    (csrc/gz_prdc.hip); the 32 bytes of integer totals are all that travels to the host, where the four quotients are
+    taken.  ``rad_r`` / ``rad_g``: radii already known as fp64 device tensors (``RealStatistics.radii`` keeps the real
+    set's).  -> the same keys as ``prdc``: four floats, and ``in_real`` / ``in_fake`` (int32), ``near``, ``rad_g``,
+    ``rad_r`` as device tensors.  No CPU fallback."""
+    from . import functional as F
+    from ._lib import check, lib
+    g = _fp64_device_codes(codes_g, "precision / recall / density / coverage", "eval.prdc")
+    r = _fp64_device_codes(codes_r, "precision / recall / density / coverage", "eval.prdc")
+    if r.device != g.device:
+        raise ValueError("the two code sets lie on different devices (%s, %s)" % (g.device, r.device))
+    k = _prdc_check(k, g, r)
+    (n_g, d), n_r = g.shape, r.shape[0]
+
+    def radii(given, codes):
+        if given is None:
+            return knn_radii_device(codes, k)
+        if (not isinstance(given, torch.Tensor) or given.dtype != torch.float64 or given.device != codes.device
+                or tuple(given.shape) != (codes.shape[0],)):
+            raise ValueError("radii must be a float64 [%d] tensor on %s" % (codes.shape[0], codes.device))
+        return given.contiguous()
+
+    rad_g, rad_r = radii(rad_g, g), radii(rad_r, r)
+    with torch.cuda.device(g.device):
+        in_real = torch.empty((n_g,), dtype=torch.int32, device=g.device)
+        in_fake = torch.empty((n_r,), dtype=torch.int32, device=g.device)
+        near = torch.empty((n_r,), dtype=torch.float64, device=g.device)
+        totals = torch.empty((4,), dtype=torch.int64, device=g.device)
+        ws_bytes = lib.gz_prdc_counts_workspace_bytes(n_g, n_r, d)
+        ws = torch.empty(max(ws_bytes, 8), dtype=torch.uint8, device=g.device)
+        check(lib.gz_prdc_counts(F._p(g), n_g, F._p(rad_g), F._p(r), n_r, F._p(rad_r), d, F._p(in_real), F._p(in_fake),
+                                 F._p(near), F._p(totals), F._p(ws), ws_bytes, F._stream()), "prdc_counts")
+        precise, recalled, inside, covered = totals.tolist()
+    return {"precision": precise / n_g, "recall": recalled / n_r, "density": inside / (k * n_g),
+            "coverage": covered / n_r, "in_real": in_real, "in_fake": in_fake, "near": near, "rad_g": rad_g,
+            "rad_r": rad_r}
+
+
 def _square_fp64_device(a, what):
     if not isinstance(a, torch.Tensor) or a.dim() != 2 or a.shape[0] != a.shape[1] or a.dtype != torch.float64:
         raise ValueError("%s must be a square float64 tensor" % what)
@@ -630,6 +762,15 @@ class RealStatistics:
             mu, sigma = mean.cpu().numpy(), cov.cpu().numpy()
         self.mu, self.sigma = np.asarray(mu, dtype=np.float64), np.asarray(sigma, dtype=np.float64)
         self._root = None
+        self._radii = {}
+
+    def radii(self, k):
+        """The real codes' k-nearest-neighbour radii (``knn_radii_device``) as an fp64 device tensor, made once per run
+        and ``k`` and kept."""
+        k = int(k)
+        if k not in self._radii:
+            self._radii[k] = knn_radii_device(self.codes, k)
+        return self._radii[k]
 
     def device_root(self):
         """-> (mu, sigma, root of sigma: fp64 device tensors, iterations, converged); one ``sqrtm_psd_device`` call per
@@ -677,7 +818,7 @@ def _fid_on_device(real, mean, cov):
 
 
 def evaluate_device(module, dump, net, real, batch=250, n_subsets=100, fid_on_device=False, classifier=None,
-                    inception_splits=10):
+                    inception_splits=10, prdc_k=None):
     """``evaluate`` with everything between the generator and the metrics on the device: features at batch ``batch``
     into one resident fp64 tensor, mean / covariance through gz_feature_moments (only those two are copied to the host,
     for ``frechet_distance``), KID through ``polynomial_mmd_averages_device`` on the resident tensors -- the same subset
@@ -685,7 +826,10 @@ def evaluate_device(module, dump, net, real, batch=250, n_subsets=100, fid_on_de
     device and ``frechet_distance_device`` runs with the real set's cached root.  Returns the same dict as ``evaluate``.
     ``classifier``: ``(weight, bias)`` of the classifier head in the FID weight file; the dict then gains ``"is"`` and
     ``"is_std"``, the Inception Score over ``inception_splits`` splits of the same resident generated codes
-    (``inception_score_device`` -- the reference's statistic on that head, not on torchvision's ImageNet network)."""
+    (``inception_score_device`` -- the reference's statistic on that head, not on torchvision's ImageNet network).
+    ``prdc_k``: a neighbour count; the dict then gains ``"precision"``, ``"recall"``, ``"density"`` and ``"coverage"``
+    (``prdc_device`` on the same resident generated codes, the real set's radii from ``real.radii``), computed after KID
+    and drawing nothing, so KID's subsets are the ones it draws without it."""
     fake = device_activations(module, dump, net, batch)
     mean, cov = feature_moments_device(fake)
     if fid_on_device:
@@ -697,6 +841,9 @@ def evaluate_device(module, dump, net, real, batch=250, n_subsets=100, fid_on_de
     if classifier is not None:
         weight, bias = classifier
         out["is"], out["is_std"], _ = inception_score_device(fake, weight, bias, splits=inception_splits)
+    if prdc_k is not None:
+        m = prdc_device(fake, real.codes, k=prdc_k, rad_r=real.radii(prdc_k))
+        out.update((key, m[key]) for key in ("precision", "recall", "density", "coverage"))
     return out
 
 

@@ -57,7 +57,10 @@ RUNNER_KEYS = {"max_steps": None, "log_every": 10, "dataset_path": None, "seed":
                # with eval_on_device: the Inception Score (gan_stability's metrics/inception_score.py, splits as there) of
                # the generated codes the pass already holds, through the classifier head of the FID weight file
                # (eval.inception_score_device, csrc/gz_inception_score.hip) -- not torchvision's ImageNet network
-               "inception_score": False, "inception_score_splits": 10}
+               "inception_score": False, "inception_score_splits": 10,
+               # with eval_on_device: improved precision / recall and density / coverage over precision_recall_k nearest
+               # neighbours of the two code sets the pass already holds (eval.prdc_device, csrc/gz_prdc.hip)
+               "precision_recall": False, "precision_recall_k": 5}
 BUILTIN_DATASETS = ("synthetic", "image_folder", "tensor_file", "celeb_a", "mnist")
 AVERAGE_PREFIX = "generator_average."     # state_dict keys of the averaged generator's parameters, next to generator.*
 LIGHTNING_VERSION_TAG = "1.2.0"       # envelope layout written below (Lightning 1.1 / 1.2 generation)
@@ -100,6 +103,9 @@ def check_eval_keys(run):
     if run.get("inception_score", False) and not run.get("eval_on_device", False):
         raise SystemExit("inception_score=true is honoured only together with eval_on_device=true: the device Inception "
                          "Score reads the codes the device evaluation pass leaves on the GPU")
+    if run.get("precision_recall", False) and not run.get("eval_on_device", False):
+        raise SystemExit("precision_recall=true is honoured only together with eval_on_device=true: the device precision, "
+                         "recall, density and coverage read the codes the device evaluation pass leaves on the GPU")
 
 
 def _builtin_dataset(name, run, filepaths):
@@ -718,17 +724,21 @@ def wants_fid(cfg, run):
 
 
 def device_fid_evaluator(dump, features, real_act, device, batch=250, average=None, mu=None, sigma=None,
-                         fid_on_device=False, inception_score=False, inception_splits=10):
+                         fid_on_device=False, inception_score=False, inception_splits=10, prdc_k=None):
     """The ``evaluate`` hook of fit() on the device pass (eval.evaluate_device).  The real set's device codes and its
     mean / covariance (``mu`` / ``sigma`` when a cache file holds them, else one moments launch) are made here, once per
     run; every epoch then costs the generated set alone.  ``fid_on_device``: the Frechet distance on the device as well
     (the real covariance's square root is made by the first evaluation and kept).  ``inception_score``: the Inception
     Score over ``inception_splits`` splits as well, through the classifier head of the weight file (``features.net.fc``,
     widened to fp64 on the device here, once per run; not the reference's torchvision network:
-    eval.inception_score_from_logits); the best checkpoint stays chosen by FID."""
+    eval.inception_score_from_logits); the best checkpoint stays chosen by FID.  ``prdc_k``: precision, recall, density
+    and coverage over that many nearest neighbours as well (eval.prdc_device; the real set's radii are made by the first
+    evaluation and kept)."""
     from . import eval as E
     real = E.RealStatistics(real_act, device, mu=mu, sigma=sigma)
     extra = {"fid_on_device": True} if fid_on_device else {}
+    if prdc_k is not None:
+        extra["prdc_k"] = int(prdc_k)
     if inception_score:
         fc = features.net.fc
         extra["classifier"] = tuple(t.detach().to(device).to(torch.float64).contiguous() for t in (fc.weight, fc.bias))
@@ -740,6 +750,8 @@ def device_fid_evaluator(dump, features, real_act, device, batch=250, average=No
         line = "epoch %d FID: %.4f KID mean: %.6f KID stddev: %.6f" % (epoch, m["fid"], m["kid"], m["kid_std"])
         if inception_score:
             line += " IS: %.4f +- %.4f" % (m["is"], m["is_std"])
+        if prdc_k is not None:
+            line += " P: %.4f R: %.4f D: %.4f C: %.4f" % (m["precision"], m["recall"], m["density"], m["coverage"])
         print(line)
         return m
 
@@ -775,6 +787,8 @@ def make_fid_evaluator(cfg, run, module, device, average=None):
         score = {}
         if run.get("inception_score", False):
             score = {"inception_score": True, "inception_splits": int(run.get("inception_score_splits", 10))}
+        if run.get("precision_recall", False):
+            score["prdc_k"] = int(run.get("precision_recall_k", 5))
         return device_fid_evaluator(dump, features, real_act, device, batch=int(run.get("eval_batch_size", 250)),
                                     average=average, mu=mu, sigma=sigma,
                                     fid_on_device=bool(run.get("fid_on_device", False)), **score)
