@@ -17,7 +17,8 @@
 //   bn_slice(_walk)       the workgroup decode and slice walk of the two fused BatchNorm kernels
 //   ew4_range             the float4 grid-stride loop of the elementwise kernels
 // Every piece fixes an ORDER of floating-point operations; tests/test_norm_parent_bits_gpu.py holds all of them to
-// recorded bits.
+// recorded bits.  What says the bits are RIGHT is tests/test_norm_fp64_gpu.py, the same cases against an fp64 reference:
+// it is the test that survives a change of summation order.
 #include <type_traits>
 
 #include "gz_common.h"

@@ -9,7 +9,11 @@ Needs an MI355X and the library of the commit before that refactor (its C ABI is
 
     GZ_LIB=<that commit's libgz_hip.so> python tests/golden/make_norm_golden.py [out.npz]
 
-Refuses to write a file that the guard test would reject (a clamped variance, an activation with one side only)."""
+Refuses to write a file that the guard test would reject (a clamped variance, an activation with one side only).
+
+A file written again (after a change of summation order, or a kernel fix) is only acceptable together with a passing
+tests/test_norm_fp64_gpu.py on the library that wrote it: recorded bits say what was computed, the fp64 reference that
+it was right."""
 import os
 import sys
 import tempfile

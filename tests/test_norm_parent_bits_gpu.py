@@ -21,7 +21,6 @@ import os
 import subprocess
 import sys
 import tempfile
-import zlib
 
 import numpy as np
 import pytest
@@ -34,47 +33,18 @@ from helpers import GOLDEN_DIR  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-EPS, MOMENTUM = 1e-5, 0.1
-ACTS = {"none": (0, 0.0), "relu": (1, 0.0), "lrelu": (2, 0.2)}
+from norm_cases import (ACTS, ADAIN_SHAPES, BIG_CHANNELS, BN_SHAPES, BWD_FEW, BWD_FULL, EPS,  # noqa: E402,F401
+                        EW_COUNTS, FINALIZE_C, FINALIZE_PER, FWD_FEW, FWD_FULL, GZ_ERR_UNSUPPORTED, MOMENTUM, NBT0,
+                        ROW_SHAPES, SENTINEL, SIGMAS, STATS_FEW, STATS_FULL, adain_host, bn_fused_switches,
+                        bn_inputs_host, channel_sum_host, elementwise_acts, elementwise_host, f32 as _f32,
+                        finalize_host, rows_host, small, switches as _switches)
+
 WHOLE_LIMIT = 512           # elements; larger outputs are stored as digest + every 257th element
-SENTINEL = 123.0            # what an output buffer holds before the launch
-GZ_ERR_UNSUPPORTED = -2
-
-ROW_SHAPES = [                 # (N, C, inner)
-    (3, 5, 4),                 # q4 = 1, 64 rows per wave, 15 rows: dead sub-waves
-    (3, 5, 12),                # q4 = 3 under lpr = 4: a dead lane inside a live row
-    (2, 3, 64),                # lpr = 16
-    (2, 3, 256),               # lpr = 64
-    (2, 3, 1024),              # CACHE = 4, full
-    (2, 3, 1280),              # forward CACHE = 16 with a tail; backward CACHE = 0 under the default knob
-    (1, 2, 4096),              # forward CACHE = 16, full
-    (1, 2, 4352),              # forward CACHE = 0
-    (4, 131080, 4),            # 524320 rows: second trip of the row loop and of the float4 loop of the apply kernels
-]
-ADAIN_SHAPES = [(5, 3, 16), (5, 3, 256), (3, 2, 1024)]      # lpr 4 and 64, and the largest row the backward accepts
-BN_SHAPES = [                  # (N, C, H, W)
-    (4, 32, 4, 4),             # CB = 16
-    (4, 8, 8, 8),              # CB = 4
-    (6, 5, 8, 8),              # odd C, CB = 1
-    (16, 32, 16, 16),          # S = 2
-    (6, 4, 64, 64),            # S = 4, P = 2: the last slice is empty
-    (12, 4, 64, 64),           # as above, with groups = 2
-]
-BIG_CHANNELS = (4, 131080, 4)  # the per-channel apply index with FastDiv, past one trip of the grid
-EW_COUNTS = [4, 2097156]       # one float4, and past one trip of the grid
 
 
 # ---------------------------------------------------------------------------
-# inputs and plumbing
+# inputs (seeded on the host: norm_cases.py) and plumbing
 # ---------------------------------------------------------------------------
-def _rng(*tag):
-    return np.random.RandomState(zlib.crc32(repr(tag).encode()) & 0x7FFFFFFF)
-
-
-def _f32(a):
-    return np.ascontiguousarray(a, dtype=np.float32)
-
-
 def _dev(a):
     import torch
     return torch.from_numpy(np.ascontiguousarray(a)).cuda()
@@ -109,15 +79,12 @@ def _ok(rc, what):
     assert rc == 0, (what, rc)
 
 
+def _upload(d):
+    return {k: _dev(v) for k, v in d.items()}
+
+
 def _rows(tag, N, C, inner):
-    """x with per-row means of 1.5 +- 0.5 and sigma 0.7, mixed-sign gradients, affine parameters of each form."""
-    r = _rng("rows", tag, N, C, inner)
-    x = 1.5 + 0.5 * r.randn(N, C, 1) + 0.7 * r.randn(N, C, inner)
-    d = {"x": x, "g": r.randn(N, C, inner), "v": r.randn(N, C, inner),
-         "gamma_c": 1 + 0.3 * r.randn(C), "beta_c": 0.3 * r.randn(C),
-         "gamma_r": 1 + 0.3 * r.randn(N * C), "beta_r": 0.3 * r.randn(N * C),
-         "acc_gamma": r.randn(N * C), "acc_beta": r.randn(N * C)}
-    return {k: _dev(_f32(v)) for k, v in d.items()}
+    return _upload(rows_host(tag, N, C, inner))
 
 
 def _affine(d, apr):
@@ -131,17 +98,9 @@ def _row_coef(d, N, C, inner, apr=0, unb=0):
     return coef
 
 
-def _switches(N, C, inner, full, few):
-    return full if N * C * inner <= 65536 else few
-
-
 # ---------------------------------------------------------------------------
 # row kernels
 # ---------------------------------------------------------------------------
-FWD_FULL = [(apr, unb, act) for apr in (0, 1) for unb in (0, 1) for act in ACTS]
-FWD_FEW = [(1, 1, "lrelu")]
-
-
 def _rownorm_fwd(N, C, inner):
     d, res = _rows("fwd", N, C, inner), {}
     for apr, unb, act in _switches(N, C, inner, FWD_FULL, FWD_FEW):
@@ -156,15 +115,9 @@ def _rownorm_fwd(N, C, inner):
 
 def _rownorm_stats(N, C, inner):
     d, res = _rows("stats", N, C, inner), {}
-    for apr, unb in _switches(N, C, inner, [(0, 0), (0, 1), (1, 0), (1, 1)], [(1, 0)]):
+    for apr, unb in _switches(N, C, inner, STATS_FULL, STATS_FEW):
         res["apr%d_unb%d/coef" % (apr, unb)] = _host(_row_coef(d, N, C, inner, apr, unb))
     return res
-
-
-# (affine_per_row, unbiased, activation, with dx); affine_per_row 2 is the packed [N][2C] gradient of AdaIN
-BWD_FULL = ([(apr, unb, act, 1) for apr in (0, 1) for unb in (0, 1) for act in ACTS]
-            + [(2, 1, "relu", 1), (1, 0, "lrelu", 0)])
-BWD_FEW = [(0, 1, "relu", 1)]
 
 
 def _norm_act_bwd_rows_form(N, C, inner):
@@ -191,7 +144,7 @@ def _rownorm_bwd_acc(N, C, inner):
     d, res = _rows("acc", N, C, inner), {}
     coef = _row_coef(d, N, C, inner)
     for acc in (0, 1):
-        for act in (ACTS if N * C * inner <= 65536 else ["lrelu"]):
+        for act in (ACTS if small(N, C, inner) else ["lrelu"]):
             dx, kbuf, ws = _buf(N, C, inner), _buf(2 * N * C), _ws(N, C)
             dgamma, dbeta = d["acc_gamma"][:C].clone(), d["acc_beta"][:C].clone()
             _ok(_lib().gz_rownorm_act_bwd_acc(_p(d["g"]), _p(d["x"]), _p(coef), _p(dx), _p(dgamma), _p(dbeta), _p(ws),
@@ -204,7 +157,7 @@ def _rownorm_bwd_acc(N, C, inner):
 def _rownorm_bwd_rows(N, C, inner):
     d, res = _rows("rows", N, C, inner), {}
     coef = _row_coef(d, N, C, inner)
-    for act in (ACTS if N * C * inner <= 65536 else ["relu"]):
+    for act in (ACTS if small(N, C, inner) else ["relu"]):
         dx, sums = _buf(N, C, inner), _buf(N * C, 2)
         _ok(_lib().gz_rownorm_act_bwd_rows(_p(d["g"]), _p(d["x"]), _p(coef), _p(dx), _p(sums), N, C, inner, *ACTS[act],
                                            None), "rownorm_act_bwd_rows")
@@ -215,7 +168,7 @@ def _rownorm_bwd_rows(N, C, inner):
 def _rownorm_bwd2(N, C, inner):
     d, res = _rows("bwd2", N, C, inner), {}
     coef = _row_coef(d, N, C, inner)
-    for act in (ACTS if N * C * inner <= 65536 else ["lrelu"]):
+    for act in (ACTS if small(N, C, inner) else ["lrelu"]):
         gg, gx, ggamma, ws = _buf(N, C, inner), _buf(N, C, inner), _buf(C), _ws(N, C)
         _ok(_lib().gz_rownorm_act_bwd2(_p(d["g"]), _p(d["v"]), _p(d["x"]), _p(coef), _p(gg), _p(gx), _p(ggamma), _p(ws),
                                        N, C, inner, *ACTS[act], None), "rownorm_act_bwd2")
@@ -226,7 +179,7 @@ def _rownorm_bwd2(N, C, inner):
 def _rownorm_sigma(N, C, inner):
     d, res = _rows("sigma", N, C, inner), {}
     for groups in (1, 2):
-        sigma = _dev(_f32([1.3, 0.8][:groups]))
+        sigma = _dev(_f32(SIGMAS[:groups]))
         coef, out = _buf(4 * N * C), _buf(N, C, inner)
         _ok(_lib().gz_rownorm_act_fwd_sigma(_p(d["x"]), _p(sigma), groups, _p(coef), _p(out), N, C, inner, EPS,
                                             *ACTS["lrelu"], None), "rownorm_act_fwd_sigma")
@@ -237,10 +190,8 @@ def _rownorm_sigma(N, C, inner):
 def _adain_const(N, C, inner):
     """gz_adain_const_fwd and gz_adain_const_bwd: x is the [C][inner] constant every sample shares, sb the packed
     per-sample [N][scale C | shift C]."""
-    r = _rng("adain", N, C, inner)
-    x = _dev(_f32(1.5 + 0.5 * r.randn(C, 1) + 0.7 * r.randn(C, inner)))
-    sb = _dev(_f32(np.concatenate([1 + 0.3 * r.randn(N, C), 0.3 * r.randn(N, C)], axis=1)))
-    g, res = _dev(_f32(r.randn(N, C, inner))), {}
+    d, res = _upload(adain_host(N, C, inner)), {}
+    x, sb, g = d["x"], d["sb"], d["g"]
     for act in ("relu", "lrelu"):
         coef, out = _buf(4 * N * C), _buf(N, C, inner)
         _ok(_lib().gz_adain_const_fwd(_p(x), _p(sb), _p(coef), _p(out), N, C, inner, EPS, *ACTS[act], None),
@@ -264,21 +215,14 @@ def _adain_const_too_long(N, C, inner):
 # BatchNorm
 # ---------------------------------------------------------------------------
 def _bn_inputs(tag, N, C, inner):
-    r = _rng("bn", tag, N, C, inner)
-    x = 1.5 + 0.5 * r.randn(1, C, 1) + 0.7 * r.randn(N, C, inner)
-    halves = x.reshape(N, C, 2, inner // 2).transpose(0, 2, 1, 3)                       # [N][half][C][inner / 2]
-    partials = np.stack([halves.sum(-1), (halves * halves).sum(-1)], -1).reshape(2 * N, C, 2)
-    d = {"x": x, "g": r.randn(N, C, inner), "partials": partials, "gamma": 1 + 0.3 * r.randn(C),
-         "beta": 0.3 * r.randn(C), "rm": 0.2 * r.randn(C), "rv": 0.5 + r.rand(C), "acc_gamma": r.randn(C),
-         "acc_beta": r.randn(C)}
-    return {k: _dev(_f32(v)) for k, v in d.items()}
+    return _upload(bn_inputs_host(tag, N, C, inner))
 
 
 def _running(d, on):
     import torch
     if not on:
         return None, None, None
-    return d["rm"].clone(), d["rv"].clone(), torch.full((1,), 7, dtype=torch.int64, device="cuda")
+    return d["rm"].clone(), d["rv"].clone(), torch.full((1,), NBT0, dtype=torch.int64, device="cuda")
 
 
 def _bn_bwd(d, coef, N, C, inner, groups, act, acc, with_dx, tag, res):
@@ -296,11 +240,9 @@ def _bn_fused(N, C, H, W):
     """gz_batchnorm_act_fwd_fused, then gz_batchnorm_act_bwd_g on its coefficients.  Switches: groups, partial rows
     from the caller (two per sample) or none, running buffers and nbt or none; accumulate follows `running`; the
     affine parameters are null once and dx is null once (the backward then takes bn_bwd_finalize_kernel)."""
-    inner, res, acts = H * W, {}, list(ACTS)
+    inner, res = H * W, {}
     d = _bn_inputs("fused", N, C, inner)
-    for i, (groups, part, run) in enumerate((g, p, r) for g in (1, 2) for p in (0, 1) for r in (0, 1)):
-        act = acts[(i + 1) % 3]
-        affine, with_dx = i != 0, i != 7
+    for groups, part, run, act, affine, with_dx in bn_fused_switches():
         rm, rv, nbt = _running(d, run)
         coef, out = _buf(4 * groups * C), _buf(N, C, inner)
         ws = None if part else _ws(N, C)
@@ -345,12 +287,9 @@ def _bn_eval_coef(N, C, H, W):
 def _bn_finalize(rows, groups):
     """gz_batchnorm_finalize_g on partial rows of 32 elements each: <= 512 rows per group is the one-wavefront image,
     more the eight-wavefront one."""
-    C, per = 5, 32
-    r = _rng("finalize", rows, groups)
-    x = 1.5 + 0.5 * r.randn(1, C, 1) + 0.7 * r.randn(rows, C, per)
-    partials = _dev(_f32(np.stack([x.sum(-1), (x * x).sum(-1)], -1)))
-    d = {k: _dev(_f32(v)) for k, v in {"gamma": 1 + 0.3 * r.randn(C), "beta": 0.3 * r.randn(C), "rm": 0.2 * r.randn(C),
-                                        "rv": 0.5 + r.rand(C)}.items()}
+    C, per = FINALIZE_C, FINALIZE_PER
+    d = _upload(finalize_host(rows, groups))
+    partials = d["partials"]
     rm, rv, nbt = _running(d, True)
     coef = _buf(4 * groups * C)
     _ok(_lib().gz_batchnorm_finalize_g(_p(partials), rows, (rows // groups) * per, _p(d["gamma"]), _p(d["beta"]),
@@ -361,19 +300,16 @@ def _bn_finalize(rows, groups):
 
 
 def _channel_sum(N, C, inner):
-    x = _dev(_f32(_rng("channel_sum").randn(N, C, inner)))
+    x = _dev(channel_sum_host(N, C, inner)["x"])
     out, ws = _buf(C), _ws(N, C)
     _ok(_lib().gz_channel_sum(_p(x), _p(out), _p(ws), N, C, inner, None), "channel_sum")
     return {"plain/out": _host(out)}
 
 
 def _elementwise(count):
-    r = _rng("ew", count)
-    g, v, out = (_f32(r.randn(count)) for _ in range(3))
-    g[:4] = np.abs(g[:4]) * [1, -1, -1, 1]          # (the one-float4 case has both sides of the activation too)
-    out[:4] = np.abs(out[:4]) * [1, -1, 1, -1]
-    g, v, out, res = _dev(g), _dev(v), _dev(out), {}
-    for name, act in (list(ACTS.items()) + [("tanh", (3, 0.0))] if count <= 65536 else [("lrelu", ACTS["lrelu"])]):
+    d, res = _upload(elementwise_host(count)), {}
+    g, v, out = d["g"], d["v"], d["out"]
+    for name, act in elementwise_acts(count):
         dx = _buf(count)
         _ok(_lib().gz_act_bwd(_p(g), _p(out), _p(dx), count, *act, None), "act_bwd")
         res["act_bwd_" + name + "/dx"] = _host(dx)
