@@ -512,6 +512,27 @@ int gz_u8hwc_gather_to_nchw(const unsigned char* set, long long M, const long lo
                             float* out, long long* labels_out, int n, int H, int W, int C, float mean, float std,
                             hipStream_t stream);
 
+/* ---- DiffAugment of the discriminator's input (Zhao et al. 2020; csrc/gz_diffaug.hip) --------------
+ * Per sample n of a batch [R0 + R1, C, H, W], with params[n] = {b, s, c, th, tw, h0, w0, unused} (fp32; the integers
+ * stored as exact floats):
+ *   x1 = x + b;  x2 = m + s (x1 - m), m = channel mean of x1 per pixel;  x3 = M + c (x2 - M), M = mean(x) + b;
+ *   x4[., h, w] = x3[., h + th, w + tw] inside the image, else 0;  y = x4 with the box [h0, h0 + cut_h) x
+ *   [w0, w0 + cut_w) zeroed (the box may lie partly outside the image; cut_h = cut_w = 0: no box).
+ * y = A x + k with A = Mask . Shift . Con . Sat linear and k from b alone.  mode 0: A x + k; mode 1: A x (b ignored);
+ * mode 2: A^T x = Con . Sat . Shift^T . Mask x (b ignored) -- the adjoint of modes 0/1, whose own adjoint is mode 1.
+ * Rows [0, R0) are read from x0, rows [R0, R0 + R1) from x1 (x1 == NULL requires R1 == 0): the stacked discriminator
+ * batch [aug(real); aug(fake)] is written by one launch without a concatenation copy.  params is [R0 + R1, 8], y is
+ * [R0 + R1, C, H, W] and overlaps neither source.  One launch, no workspace, no atomics: every input element is read
+ * once and every output element written once, the sample staying in registers in between; 16-byte stores wherever
+ * the address is 16-byte aligned, any alignment of x0 / x1 / y to 4 bytes accepted.  The mean is a fixed-order
+ * reduction (equal bits on every run) whose longest chain of dependent additions is 30.  A shift or corner outside
+ * the image is clamped, never dereferenced.
+ * Supported: 1 <= C <= 4, H, W >= 4, C*H*W <= 65536; anything else returns GZ_ERR_UNSUPPORTED and launches nothing.
+ * GZ_ERR_BAD_SHAPE: a null x0 / params / y, x1 == NULL with R1 != 0, R0 or R1 negative, R0 + R1 < 1, a non-positive
+ * dimension, a negative cut size, a mode outside 0..2, or y overlapping the rows read from x0 or x1. */
+int gz_diffaug(const float* x0, const float* x1, const float* params, float* y, int R0, int R1, int C, int H, int W,
+               int cut_h, int cut_w, int mode, hipStream_t stream);
+
 /* ---- fused multi-tensor optimizer steps (the `optimiser` nodes of conf/expt/<name>.yaml) -------------------------
  * `count` <= GZ_OPT_MAX_TENSORS tensors per call (host arrays of device pointers and element counts);
  * grads are multiplied by grad_scale first (1/world for data-parallel means).  Formulas are torch.optim's

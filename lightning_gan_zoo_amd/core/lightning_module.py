@@ -15,6 +15,7 @@ import torch
 
 from .. import functional as F
 from ..config import instantiate
+from ..augment import DiffAugment
 from ..harness import LightningModule, draw_on_host
 from .utils.utils import VerboseShapeExecution, compute_grad2, gradient_penalty
 
@@ -73,6 +74,9 @@ class BaseGAN(LightningModule):
         self.criterion = instantiate(cfg.train.criterion)
         self.noise_distn = instantiate(cfg.model.noise_distn)
         self.fixed_noise = self.noise_distn.sample((8, cfg.model.noise_dim))
+        # DiffAugment of every tensor handed to the discriminator (augment.py; runner key `diffaugment`): None = off,
+        # and then every site below is the code it was before the key existed -- no launch, no host draw
+        self.diffaugment = DiffAugment(cfg.get("diffaugment", "")) or None
         if cfg.debug.verbose_shape:                      # reference :53-54
             self.apply(VerboseShapeExecution)
 
@@ -90,6 +94,17 @@ class BaseGAN(LightningModule):
             return F.bce_logits_mean(logits, value)
         return c(logits, torch.full_like(logits, value))
 
+    def augmented(self, x):
+        """``x`` as the discriminator sees it: through DiffAugment with parameters drawn at this call, or ``x`` itself."""
+        return x if self.diffaugment is None else self.diffaugment(x)
+
+    def stacked_batch(self, real, fake):
+        """[real; fake.detach()]: the concatenation, or -- augmenting -- ONE two-source launch that writes
+        [aug(real); aug(fake)] with real's parameter rows first (no concatenation copy)."""
+        if self.diffaugment is None:
+            return torch.cat([real, fake.detach()])
+        return self.diffaugment(real, fake.detach())
+
     def stacked_discriminator(self, real, fake):
         """D(cat(real, fake.detach()), groups=2).reshape(-1) -- [logits(real); logits(fake)] -- when the discriminator
         supports stacked batches, else None (the caller takes the reference's two calls)."""
@@ -97,7 +112,7 @@ class BaseGAN(LightningModule):
         if not (self.stack_d_passes and getattr(d, "supports_stacked_batches", False) and real.is_cuda and d.training
                 and real.shape == fake.shape):
             return None
-        return d(torch.cat([real, fake.detach()]), groups=2).reshape(-1)
+        return d(self.stacked_batch(real, fake), groups=2).reshape(-1)
 
     def sample_noise(self, n):
         # drawn on the host generator, then copied to the device (reference :107-108); single host
@@ -182,15 +197,15 @@ class DCGAN(BaseGAN):
                     loss_disc = F.bce_logits_pair_mean(logits, 1.0, 0.0)      # (BCE(real, 1) + BCE(fake, 0)) / 2
                     self.log("train/d_loss", loss_disc)
                     return loss_disc
-                disc_real = self.discriminator(real).reshape(-1)
+                disc_real = self.discriminator(self.augmented(real)).reshape(-1)
             elif self.real_first:
-                disc_real = self.discriminator(real).reshape(-1)
+                disc_real = self.discriminator(self.augmented(real)).reshape(-1)
                 fake = self.generator(noise)
             else:
                 fake = self.generator(noise)
-                disc_real = self.discriminator(real).reshape(-1)
+                disc_real = self.discriminator(self.augmented(real)).reshape(-1)
             loss_disc_real = self.criterion_const(disc_real, 1.0)
-            disc_fake = self.discriminator(fake.detach()).reshape(-1)
+            disc_fake = self.discriminator(self.augmented(fake.detach())).reshape(-1)
             loss_disc_fake = self.criterion_const(disc_fake, 0.0)
             loss_disc = (loss_disc_real + loss_disc_fake) / 2
             self.log("train/d_loss", loss_disc)
@@ -198,7 +213,7 @@ class DCGAN(BaseGAN):
 
         if optimizer_idx == 1:      # generator (reference :124-128)
             fake = self.generator(noise)
-            output = self.discriminator(fake).reshape(-1)
+            output = self.discriminator(self.augmented(fake)).reshape(-1)
             loss_gen = self.criterion_const(output, 1.0)
             self.log("train/g_loss", loss_gen)
             return loss_gen
@@ -213,9 +228,9 @@ class GANStabilityR1(BaseGAN):
 
         if optimizer_idx == 0:
             real.requires_grad_()
-            disc_real = self.discriminator(real).reshape(-1)
+            disc_real = self.discriminator(self.augmented(real)).reshape(-1)
             loss_disc_real = self.criterion_const(disc_real, 1.0)
-            disc_fake = self.discriminator(fake.detach()).reshape(-1)
+            disc_fake = self.discriminator(self.augmented(fake.detach())).reshape(-1)
             loss_disc_fake = self.criterion_const(disc_fake, 0.0)
             r1_reg = self.cfg.loss_weight.reg * compute_grad2(disc_real, real).mean()
             loss_disc = r1_reg + (loss_disc_real + loss_disc_fake)
@@ -223,7 +238,7 @@ class GANStabilityR1(BaseGAN):
             return loss_disc
 
         if optimizer_idx == 1:
-            output = self.discriminator(fake).reshape(-1)
+            output = self.discriminator(self.augmented(fake)).reshape(-1)
             loss_gen = self.criterion_const(output, 1.0)
             self.log("train/g_loss", loss_gen)
             return loss_gen
@@ -248,21 +263,21 @@ class WGAN(BaseGAN):
                     loss_disc = F.weighted_half_means(logits, -1.0, 1.0)      # -(mean(D(real)) - mean(D(fake)))
                     self.log("train/d_loss", loss_disc)
                     return loss_disc
-                disc_real = self.discriminator(real).reshape(-1)
+                disc_real = self.discriminator(self.augmented(real)).reshape(-1)
             elif self.real_first:
-                disc_real = self.discriminator(real).reshape(-1)
+                disc_real = self.discriminator(self.augmented(real)).reshape(-1)
                 fake = self.generator(noise)
             else:
                 fake = self.generator(noise)
-                disc_real = self.discriminator(real).reshape(-1)
-            disc_fake = self.discriminator(fake.detach()).reshape(-1)
+                disc_real = self.discriminator(self.augmented(real)).reshape(-1)
+            disc_fake = self.discriminator(self.augmented(fake.detach())).reshape(-1)
             loss_disc = -(torch.mean(disc_real) - torch.mean(disc_fake))
             self.log("train/d_loss", loss_disc)
             return loss_disc
 
         if optimizer_idx == 1:
             fake = self.generator(noise)
-            gen_fake = self.discriminator(fake).reshape(-1)
+            gen_fake = self.discriminator(self.augmented(fake)).reshape(-1)
             loss_gen = -torch.mean(gen_fake)
             self.log("train/g_loss", loss_gen)
             return loss_gen
@@ -270,6 +285,9 @@ class WGAN(BaseGAN):
 
 class WGANGP(BaseGAN):
     gp_alpha = None     # test hook: pin the interpolation coefficients ([N,1,1,1])
+
+    def augmented_critic(self, x):
+        return self.discriminator(self.augmented(x))
 
     def training_step(self, batch, batch_idx, optimizer_idx):
         real, _ = batch
@@ -283,17 +301,19 @@ class WGANGP(BaseGAN):
                 fake = self.generator(noise)
                 logits = self.stacked_discriminator(real, fake)
                 if logits is None:
-                    disc_real = self.discriminator(real).reshape(-1)
+                    disc_real = self.discriminator(self.augmented(real)).reshape(-1)
             elif self.real_first:
-                disc_real = self.discriminator(real).reshape(-1)
+                disc_real = self.discriminator(self.augmented(real)).reshape(-1)
                 fake = self.generator(noise)
             else:
                 fake = self.generator(noise)
-                disc_real = self.discriminator(real).reshape(-1)
+                disc_real = self.discriminator(self.augmented(real)).reshape(-1)
             if logits is None:
-                disc_fake = self.discriminator(fake.detach()).reshape(-1)
+                disc_fake = self.discriminator(self.augmented(fake.detach())).reshape(-1)
             # `fake` is NOT detached here, as in the reference (:195-196)
-            gp = gradient_penalty(self.discriminator, real, fake, device=self.device, alpha=self.gp_alpha)
+            # (augmenting: the critic of the penalty sees T(x_hat), the penalty is taken with respect to x_hat)
+            critic = self.discriminator if self.diffaugment is None else self.augmented_critic
+            gp = gradient_penalty(critic, real, fake, device=self.device, alpha=self.gp_alpha)
             if logits is not None:
                 loss_disc = (self.cfg.loss_weight.lambda_gp * gp) + F.weighted_half_means(logits, -1.0, 1.0)
             else:
@@ -303,7 +323,7 @@ class WGANGP(BaseGAN):
 
         if optimizer_idx == 1:
             fake = self.generator(noise)
-            gen_fake = self.discriminator(fake).reshape(-1)
+            gen_fake = self.discriminator(self.augmented(fake)).reshape(-1)
             loss_gen = -torch.mean(gen_fake)
             self.log("train/g_loss", loss_gen)
             return loss_gen
@@ -326,7 +346,7 @@ class HOLOGAN(BaseGAN):
                 # iteration (real's first, as in the reference's call order) -- hologan_discriminator.Discriminator
                 fake = self.generator(z)
                 if real.shape == fake.shape:
-                    logits, d_z_pred = d(torch.cat([real, fake.detach()]), groups=2)
+                    logits, d_z_pred = d(self.stacked_batch(real, fake), groups=2)
                     loss_disc = F.bce_logits_pair_mean(logits, 1.0, 0.0)       # (BCE(real, 1) + BCE(fake, 0)) / 2
                     q_loss = F.mse_mean(d_z_pred[len(real):], z)
                     self.log("train/d_loss", loss_disc)
@@ -335,15 +355,15 @@ class HOLOGAN(BaseGAN):
             # (the generator draws its views from numpy's generator inside forward(): no other numpy draw happens in
             # this step, so running D(real) first leaves that stream untouched)
             if fake is not None:
-                disc_real, _ = self.discriminator(real)
+                disc_real, _ = self.discriminator(self.augmented(real))
             elif self.real_first:
-                disc_real, _ = self.discriminator(real)
+                disc_real, _ = self.discriminator(self.augmented(real))
                 fake = self.generator(z)
             else:
                 fake = self.generator(z)
-                disc_real, _ = self.discriminator(real)
+                disc_real, _ = self.discriminator(self.augmented(real))
             loss_disc_real = self.criterion_const(disc_real, 1.0)
-            disc_fake, d_z_pred = self.discriminator(fake.detach())
+            disc_fake, d_z_pred = self.discriminator(self.augmented(fake.detach()))
             loss_disc_fake = self.criterion_const(disc_fake, 0.0)
             loss_disc = (loss_disc_real + loss_disc_fake) / 2
             q_loss = F.mse_mean(d_z_pred, z)
@@ -353,7 +373,7 @@ class HOLOGAN(BaseGAN):
 
         if optimizer_idx == 1:
             fake = self.generator(z)
-            output, d_z_pred = self.discriminator(fake)
+            output, d_z_pred = self.discriminator(self.augmented(fake))
             loss_gen = self.criterion_const(output, 1.0)
             q_loss = F.mse_mean(d_z_pred, z)
             self.log("train/g_loss", loss_gen)

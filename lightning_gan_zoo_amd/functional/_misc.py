@@ -489,4 +489,78 @@ def figure_frames_u8(img, frames, ncol, padding=2, pad_value=0.0):
           "figure_frames_u8")
     return out
 
+
+
+# ---------------------------------------------------------------------------
+# DiffAugment of the discriminator's input (csrc/gz_diffaug.hip; DESIGN.md 3.5).  y = A x + k per sample with A linear
+# once the parameters are drawn: the forward (mode 0 / 1), its adjoint (mode 2) and the adjoint's adjoint (mode 1) are
+# one kernel, so the pair below closes under differentiation like _RowScale / _RowDot.
+# ---------------------------------------------------------------------------
+def _diffaug_raw(x, x1, params, cut, mode):
+    x, params = _req(x, "x"), _req(params, "params")
+    if x.dim() != 4:
+        raise RuntimeError("lightning_gan_zoo_amd: expected an NCHW tensor, got shape %s" % (tuple(x.shape),))
+    R0, C, H, W = x.shape
+    R1 = 0
+    if x1 is not None:
+        x1 = _req(x1, "x1")
+        if x1.dim() != 4 or x1.shape[1:] != x.shape[1:]:
+            raise RuntimeError("lightning_gan_zoo_amd: diffaugment sources differ in shape: %s and %s"
+                               % (tuple(x.shape), tuple(x1.shape)))
+        R1 = x1.shape[0]
+    if tuple(params.shape) != (R0 + R1, 8):
+        raise RuntimeError("lightning_gan_zoo_amd: diffaugment params must be [%d, 8], got %s"
+                           % (R0 + R1, tuple(params.shape)))
+    y = torch.empty((R0 + R1, C, H, W), device=x.device, dtype=torch.float32)
+    check(lib.gz_diffaug(_p(x), _p(x1), _p(params), _p(y), R0, R1, C, H, W, int(cut[0]), int(cut[1]), mode, _stream()),
+          "diffaug")
+    return y
+
+
+class _DiffAug(torch.autograd.Function):
+    """[A x + k; A x1 + k] (affine) or [A x; A x1] (the adjoint's derivative) -- gz_diffaug modes 0 and 1."""
+
+    @staticmethod
+    def forward(ctx, x, x1, params, cut, affine):
+        ctx.save_for_backward(params)
+        ctx.cut, ctx.r0 = cut, x.shape[0]
+        return _diffaug_raw(x, x1, params, cut, 0 if affine else 1)
+
+    @staticmethod
+    def backward(ctx, g):
+        (params,) = ctx.saved_tensors
+        r0, (need0, need1) = ctx.r0, ctx.needs_input_grad[:2]
+        g0 = g1 = None
+        if need0 and need1:                    # one adjoint launch over the stacked rows
+            gx = _DiffAugT.apply(g, params, ctx.cut)
+            g0, g1 = gx[:r0], gx[r0:]
+        elif need0:
+            g0 = _DiffAugT.apply(g[:r0], params[:r0], ctx.cut)
+        elif need1:
+            g1 = _DiffAugT.apply(g[r0:], params[r0:], ctx.cut)
+        return g0, g1, None, None, None
+
+
+class _DiffAugT(torch.autograd.Function):
+    """A^T g -- gz_diffaug mode 2; its derivative with respect to g is A again."""
+
+    @staticmethod
+    def forward(ctx, g, params, cut):
+        ctx.save_for_backward(params)
+        ctx.cut = cut
+        return _diffaug_raw(g, None, params, cut, 2)
+
+    @staticmethod
+    def backward(ctx, v):
+        (params,) = ctx.saved_tensors
+        return _DiffAug.apply(v, None, params, ctx.cut, False), None, None
+
+
+def diffaugment(x, params, cut, x1=None):
+    """DiffAugment of ``x`` [R0, C, H, W] (and ``x1`` [R1, C, H, W], stacked behind it: [aug(x); aug(x1)] from one launch,
+    no concatenation copy) with the drawn per-sample ``params`` [R0 + R1, 8] = (b, s, c, th, tw, h0, w0, 0) and the
+    cutout size ``cut`` = (cut_h, cut_w).  Differentiable to any order in ``x`` / ``x1``; ``params`` gets no gradient."""
+    return _DiffAug.apply(x, x1, params, (int(cut[0]), int(cut[1])), True)
+
+
 __all__ = [n for n in list(globals()) if not n.startswith("__")]     # the flat namespace of the package (private helpers included)

@@ -299,11 +299,15 @@ class GraphedTrainer(Trainer):
     learning rates (and the batch shape) it was captured with: after ``end_epoch()`` has moved a scheduler, or when
     the data set's last batch is smaller, the step is captured again instead of replaying stale arguments.
     Restrictions (enforced): single process (no GradSync), fused optimizers (Adam with a device-side step counter,
-    RMSprop)."""
+    RMSprop), no DiffAugment (its per-call draws are not staged)."""
 
     def __init__(self, module, warmup=2, grad_sync=None, generator_average=None):
         if grad_sync is not None:
             raise RuntimeError("GraphedTrainer is single-process: the data-parallel gradient exchange is not captured")
+        if getattr(module, "diffaugment", None) is not None:
+            raise RuntimeError("GraphedTrainer does not capture a step that augments (config key diffaugment=%s): the "
+                               "per-call parameter draws are host work that is not staged for replay; use Trainer"
+                               % ",".join(module.diffaugment.groups))
         super().__init__(module, generator_average=generator_average)
         from . import functional as F
         self._F = F

@@ -60,7 +60,10 @@ RUNNER_KEYS = {"max_steps": None, "log_every": 10, "dataset_path": None, "seed":
                "inception_score": False, "inception_score_splits": 10,
                # with eval_on_device: improved precision / recall and density / coverage over precision_recall_k nearest
                # neighbours of the two code sets the pass already holds (eval.prdc_device, csrc/gz_prdc.hip)
-               "precision_recall": False, "precision_recall_k": 5}
+               "precision_recall": False, "precision_recall_k": 5,
+               # DiffAugment of the discriminator's input (augment.py, csrc/gz_diffaug.hip): a comma-separated subset of
+               # color, translation, cutout; "" = off.  Travels into the module's cfg as cfg.diffaugment
+               "diffaugment": ""}
 BUILTIN_DATASETS = ("synthetic", "image_folder", "tensor_file", "celeb_a", "mnist")
 AVERAGE_PREFIX = "generator_average."     # state_dict keys of the averaged generator's parameters, next to generator.*
 LIGHTNING_VERSION_TAG = "1.2.0"       # envelope layout written below (Lightning 1.1 / 1.2 generation)
@@ -93,7 +96,17 @@ def parse_overrides(argv):
     if expt is None:
         raise SystemExit("missing +expt=<dc_gan|wgan|wgan_gp|hologan|gan_stability_r1>")
     check_eval_keys(runner)
+    check_diffaugment(runner)
     return conf_dir, expt, rest, runner
+
+
+def check_diffaugment(run):
+    """The policy as the canonical comma-separated string ('' = off); a bad one ends the run with the parser's message."""
+    from .augment import parse_policy
+    try:
+        run["diffaugment"] = ",".join(parse_policy(run.get("diffaugment", "")))
+    except ValueError as e:
+        raise SystemExit(str(e)) from e
 
 
 def check_eval_keys(run):
@@ -136,13 +149,16 @@ def _builtin_dataset(name, run, filepaths):
 def compose(conf_dir, expt, overrides, run=None):
     """The experiment's config: from ``conf_dir`` when given, else from the built-in tree."""
     run = run or dict(RUNNER_KEYS)
+    check_diffaugment(run)
     if conf_dir:
         from . import dropin
         dropin.install()
         try:
-            return compose_tree(conf_dir, overrides)
+            cfg = compose_tree(conf_dir, overrides)
         except ConfigError as e:
             raise SystemExit("config error: %s" % e) from e
+        cfg["diffaugment"] = run["diffaugment"]       # read by BaseGAN.__init__
+        return cfg
     dotted, dataset, filepaths = {}, "synthetic", {}
     for arg in overrides:
         key, text = arg.split("=", 1)
@@ -172,6 +188,7 @@ def compose(conf_dir, expt, overrides, run=None):
             raise SystemExit("unknown config key %r" % key)
     cfg = make_cfg(expt, dotted=dotted)
     cfg["dataset"] = _to_cfg(_builtin_dataset(dataset, run, filepaths))
+    cfg["diffaugment"] = run["diffaugment"]           # read by BaseGAN.__init__
     cfg.train["channels_img"] = cfg.dataset.get("n_channels", 3) if "train.channels_img" not in dotted else \
         cfg.train["channels_img"]
     return cfg
