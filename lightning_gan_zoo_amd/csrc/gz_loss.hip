@@ -35,14 +35,16 @@ __global__ __launch_bounds__(LT) void bce_logits_mean_kernel(const float* __rest
     if (threadIdx.x == 0) loss[0] = s / (float)n;
 }
 
+// 1 / (1 + e^-v).  Below -88.7 e^-v overflows float32 and the quotient came out as 0 where the value is e^v (8e-40 at
+// -90, against target 0 the whole gradient); from -87 down 1 + e^-v == e^-v in float32, so e^v IS the quotient there.
+// Every other logit keeps the expression, and the bits, it had.
+__device__ __forceinline__ float sigmoid_f(float v) { return v < -87.f ? expf(v) : 1.f / (1.f + expf(-v)); }
+
 // dx = (sigmoid(x) - t) * g / n
 __global__ __launch_bounds__(LT) void bce_logits_mean_bwd_kernel(const float* __restrict__ x, const float* __restrict__ g,
                                                                 float* __restrict__ dx, int n, float t) {
     const float scale = g[0] / (float)n;
-    for (int i = blockIdx.x * LT + threadIdx.x; i < n; i += gridDim.x * LT) {
-        const float v = x[i];
-        dx[i] = (1.f / (1.f + expf(-v)) - t) * scale;
-    }
+    for (int i = blockIdx.x * LT + threadIdx.x; i < n; i += gridDim.x * LT) dx[i] = (sigmoid_f(x[i]) - t) * scale;
 }
 
 // Loss head of a discriminator step on the stacked batch [real; fake] (round 4): logits x[0..n) against t0 and
@@ -74,7 +76,7 @@ __global__ __launch_bounds__(LT) void pair_loss_bwd_kernel(const float* __restri
     const float gs = g[0] / (float)n;
     for (int i = blockIdx.x * LT + threadIdx.x; i < 2 * n; i += gridDim.x * LT) {
         const float t = i < n ? t0 : t1;
-        dx[i] = mode == 0 ? (1.f / (1.f + expf(-x[i])) - t) * (gs * 0.5f) : t * gs;
+        dx[i] = mode == 0 ? (sigmoid_f(x[i]) - t) * (gs * 0.5f) : t * gs;
     }
 }
 

@@ -16,6 +16,8 @@ magnitude s >= |v|:
     a * b          ->  s_a |b| + |a| s_b - |a b|       (first order: each factor's error times the other's value; equal
                                                         to |a b| when both factors are exact)
     sum_i a_i      ->  sum_i s_i ;     a * const, a / const  ->  s * |const|
+    sqrt(a)        ->  s_a / (2 sqrt|a|) ;     a / b  ->  s_a / |b| + |a| s_b / b^2      (first order; used by
+                                                        tail_reference.py, no formula of this module needs them)
     input          ->  s = |v|
 so that a result which is a small difference of large terms is allowed the error of the large terms and no more.  Two
 quantities enter this arithmetic with a scale of their own:
@@ -124,7 +126,13 @@ class T:
         return T(self.v * o.v, self.s * o.v.abs() + self.v.abs() * o.s - (self.v * o.v).abs())
 
     def __truediv__(self, c):
+        if isinstance(c, T):        # first order: s_a / |b| + |a| s_b / b^2
+            return T(self.v / c.v, self.s / c.v.abs() + self.v.abs() * c.s / (c.v * c.v))
         return T(self.v / c, self.s / abs(c))
+
+    def sqrt(self):                 # first order: s_a / (2 sqrt|a|); an exact zero stays exact
+        r = self.v.abs().sqrt()
+        return T(r, torch.where(r > 0, self.s / (2 * r), torch.zeros_like(r)))
 
     def __neg__(self):
         return T(-self.v, self.s)
@@ -659,26 +667,27 @@ def ratios(got, ref, Kk=None):
     return q
 
 
-def compare(got, ref, key=""):
-    """[] or one message: the key, the count and the first few positions, values and ratios to tolerance."""
-    got = np.asarray(got)
+def compare(got, ref, key="", table=None):
+    """[] or one message: the key, the count and the first few positions, values and ratios to tolerance.
+    table: the K of another reference module that shares this comparator (tail_reference.py)."""
+    got, table = np.asarray(got), K if table is None else table
     if got.size != ref.value.size:
         return ["%s: %d elements against %d" % (key, got.size, ref.value.size)]
     if ref.kind == "int":
         same = got.dtype.kind in "iu" and np.array_equal(got.reshape(-1), ref.value.reshape(-1))
         return [] if same else ["%s: %s against %s" % (key, got.reshape(-1)[:4], ref.value.reshape(-1)[:4])]
-    q = ratios(got, ref)
+    q = ratios(got, ref, table[ref.kind])
     bad = np.argwhere(~(q <= 1.0))
     if not bad.size:
         return []
     at = tuple(bad[:4].T)
     return ["%s: %d of %d beyond K = %d (%s), first at %s: got %s, reference %s, ratio to tolerance %s"
-            % (key, len(bad), q.size, K[ref.kind], ref.kind, bad[:4].tolist(), got.reshape(ref.value.shape)[at],
+            % (key, len(bad), q.size, table[ref.kind], ref.kind, bad[:4].tolist(), got.reshape(ref.value.shape)[at],
                ref.value[at], q[at])]
 
 
-def worst(got, ref):
-    return 0.0 if ref.kind == "int" else float(ratios(got, ref).max())
+def worst(got, ref, table=None):
+    return 0.0 if ref.kind == "int" else float(ratios(got, ref, (K if table is None else table)[ref.kind]).max())
 
 
 # ---------------------------------------------------------------------------
