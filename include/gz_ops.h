@@ -695,6 +695,66 @@ int gz_prdc_counts(const double* codes_g, long long n_g, const double* rad_g, co
                    void* workspace, size_t ws_bytes, hipStream_t stream);
 int gz_prdc_plan(long long n_rows, long long n_cols, int* row_groups, int* col_slices);
 
+/* ---- sliced Wasserstein distance on Laplacian-pyramid patches (csrc/gz_swd.hip) ------------------------
+ * The metric of Karras et al. 2018 (section 5 and appendix) from pixels alone: eval.swd is the definition, eval.swd_device
+ * strings these launchers together.  All of them: fp32 (statistics and sums fp64) DEVICE arrays, wave64 vector code, no
+ * atomics, every sum in a fixed order, no output or workspace read before this call wrote it: two calls give equal bits.
+ * No launcher allocates or synchronises.
+ *
+ * gz_swd_pyramid: x [N][C][S][S] -> the Laplacian levels S, S/2, .., 16 packed into out: level l is [N][C][S_l][S_l] at
+ * float offset offsets[l] (gz_swd_pyramid_describe: levels, offsets[0 .. levels], the last one the total).  down: the
+ * 5 taps [1,4,6,4,1]/16 along W, then along H, mirror border (-1 -> 1, n -> n - 2), even rows and columns; up: zeros at the
+ * odd positions, the same taps * 2 along H, then along W; L_l = G_l - up(G_l+1), the coarsest level is G itself.  Each tap
+ * sum runs t = 0 .. 4 in order.  One workgroup per plane keeps every level of it in LDS (127 KiB at S = 128): x is read once,
+ * each level written once.  One launch.  GZ_ERR_UNSUPPORTED: S not in {16, 32, 64, 128}; GZ_ERR_BAD_SHAPE: N < 1, C not 1
+ * or 3, a null pointer; GZ_ERR_WORKSPACE: out_elems below the total.
+ *
+ * Patches: pos [rows][2] int32 holds (cy, cx) of row r = image * P + patch, rows = n * P, centres in [3, H - 3) (a centre
+ * outside is clamped into it, never dereferenced outside the plane).  Descriptor element k = (c * 7 + dy) * 7 + dx is
+ * level[image][c][cy - 3 + dy][cx - 3 + dx], D = 49 C.
+ *
+ * gz_swd_channel_stats: stats[c] = mean, stats[C + c] = population standard deviation of channel c over the rows * 49
+ * gathered values, 2 C doubles.  Sums of v - v0 and (v - v0)^2 in fp64, v0 = the channel's first gathered value (row 0, tap
+ * 0), so that a constant channel gives a standard deviation of exactly 0: thread-strided rows, the xor butterfly, waves in
+ * order, workgroups in order.  Two launches; workspace gz_swd_channel_stats_workspace_bytes.
+ *
+ * gz_swd_project: proj[j][r] = sum_k x_rk dirs[j][k] for j < ndirs, r < rows, with x_rk = (d_rk - (float)mean_c) *
+ * (float)(1 / std_c) (std_c == 0 divides by 1) from stats as gz_swd_channel_stats writes it.  fp32, in this order: the 7 products
+ * of one patch row (c, dy) form one chain of fused multiply-adds from 0, dx ascending; the 7 C chain results are added to
+ * one total in (c, dy) order -- 7 + 7 C roundings on any path, which the tests' error bound rests on.  Descriptors never
+ * reach memory: a workgroup gathers 128 rows
+ * into LDS beside 128 directions (147 KiB).  proj has row pitch `pitch` >= the sort's padded length (gz_swd_sort_plan);
+ * entries rows .. padded - 1 of every direction are set to +inf, entries beyond are not touched.  One launch.
+ *
+ * gz_swd_sort_columns: every one of `cols` arrays data[j * pitch + 0 .. rows - 1] ascending, in place, by a bitonic
+ * network on the keys' bits mapped to order-preserving integers (-0.0 below +0.0, no NaN handling).  Entries rows ..
+ * padded - 1 come out +inf whatever they held; entries padded .. pitch - 1 are not touched.  A block pass sorts or merges
+ * `block` keys in one workgroup (strides below 16 in registers, 16 .. 512 by lane exchange, above through LDS); a global
+ * pass is one compare-exchange stride >= block, or two of them fused (a phase's strides go two to a pass while two are
+ * left), with 16-byte accesses.  gz_swd_sort_plan: block, padded = the power of two >= rows,
+ * and the number of block and global passes (launches).  pitch % 4 == 0 and data 16-byte aligned.
+ *
+ * gz_swd_distance: out[q] = sum over the columns q * cols_per_repeat .. (q + 1) * cols_per_repeat - 1 and rows of
+ * |a - b| in fp64 (the caller divides by rows * cols_per_repeat), q < repeats.  Thread-strided rows of one column per
+ * workgroup and row chunk, butterfly, waves in order, then the chunks and columns of a repeat in order.  Two launches;
+ * workspace gz_swd_distance_workspace_bytes.  GZ_ERR_BAD_SHAPE: rows_a != rows_b.
+ *
+ * Everywhere: GZ_ERR_BAD_SHAPE for a count below 1 (P = 0 included), a null pointer, a pitch below the padded length;
+ * GZ_ERR_TOO_LARGE for a grid beyond 2^31 - 1; GZ_ERR_WORKSPACE for a short workspace.  A refused call launches nothing;
+ * the size queries return 0 for a refused shape. */
+int gz_swd_pyramid_describe(int N, int C, int S, int* levels, long long* offsets);
+int gz_swd_pyramid(const float* x, int N, int C, int S, float* out, long long out_elems, hipStream_t stream);
+size_t gz_swd_channel_stats_workspace_bytes(int n, int C, int H, int P);
+int gz_swd_channel_stats(const float* level, int n, int C, int H, const int* pos, int P, double* stats,
+                         void* workspace, size_t ws_bytes, hipStream_t stream);
+int gz_swd_project(const float* level, int n, int C, int H, const int* pos, int P, const double* stats,
+                   const float* dirs, int ndirs, float* proj, long long pitch, hipStream_t stream);
+int gz_swd_sort_plan(long long rows, int* block, long long* padded, int* block_passes, int* global_passes);
+int gz_swd_sort_columns(float* data, long long rows, int cols, long long pitch, hipStream_t stream);
+size_t gz_swd_distance_workspace_bytes(long long rows, int cols_per_repeat, int repeats);
+int gz_swd_distance(const float* a, long long rows_a, const float* b, long long rows_b, int cols_per_repeat, int repeats,
+                    long long pitch, double* out, void* workspace, size_t ws_bytes, hipStream_t stream);
+
 /* text of the last HIP error seen by a launcher on the calling thread ("" if none) */
 const char* gz_last_error(void);
 

@@ -25,7 +25,7 @@ DIGEST_SOURCE = "gz_build_id.hip"          # holds gz_source_digest(); compiled 
 # (longest compile first: the pool takes the list in order, and gz_conv.hip alone is most of a build's wall time)
 SOURCES = ["gz_conv.hip", "gz_conv3d.hip", "gz_conv_direct.hip", "gz_pack.hip", "gz_norm.hip", "gz_misc.hip", "gz_resample.hip", "gz_optim.hip",
            "gz_resnet.hip", "gz_loss.hip", "gz_infer.hip", "gz_figures.hip", "gz_ema.hip", "gz_kid.hip", "gz_moments.hip",
-           "gz_sqrtm.hip", "gz_inception_score.hip", "gz_prdc.hip", "gz_diffaug.hip"]
+           "gz_sqrtm.hip", "gz_inception_score.hip", "gz_prdc.hip", "gz_diffaug.hip", "gz_swd.hip"]
 FLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-I", INCLUDE]
 
 

@@ -24,6 +24,12 @@ With ``classifier=`` it also reports the Inception Score (gan_stability's metric
 codes: ``inception_score_device`` on csrc/gz_inception_score.hip, ``inception_score_from_logits`` its host yardstick.
 With ``prdc_k=`` it reports improved precision / recall and density / coverage of the two resident code sets as well:
 ``prdc_device`` on csrc/gz_prdc.hip, ``prdc`` its host yardstick (the reference has neither).
+
+``evaluate_swd`` is a metric that needs none of that -- no network, no weight file: the sliced Wasserstein distance on
+Laplacian-pyramid patches (Karras et al. 2018), one number per resolution level, from the pixels of a real and a generated
+set alone.  ``swd`` (with ``laplacian_pyramid``, ``swd_descriptors``, ``sliced_wasserstein``) is its definition in numpy
+fp64, ``swd_device`` the same statistic on csrc/gz_swd.hip, ``SwdPlan`` its draws, ``RealPyramid`` the real set's resident
+side (the reference has no such metric).
 """
 import numpy as np
 import torch
@@ -885,3 +891,344 @@ def fid_from_weight_file(module, real_images_u8, weights=None, n_samples=5000, b
     else:
         real_act = features(real_images_u8)
     return evaluate(module, dump, features, real_act, n_subsets=n_subsets)
+
+
+# ---------------------------------------------------------------------------------------------------------
+# sliced Wasserstein distance on Laplacian-pyramid patches (Karras et al. 2018, section 5 and appendix).
+# The reference has no such metric: the functions below ARE its definition here.  Numpy fp64 yardsticks first, then the
+# same statistic on csrc/gz_swd.hip.
+# ---------------------------------------------------------------------------------------------------------
+SWD_SIZES = (16, 32, 64, 128)
+SWD_TAPS = np.array([1.0, 4.0, 6.0, 4.0, 1.0]) / 16.0
+SWD_PATCH = 7
+
+
+def swd_level_sizes(size):
+    """S, S/2, .., 16."""
+    if size not in SWD_SIZES:
+        raise ValueError("the sliced Wasserstein distance takes square images of size %s, got %r" % (SWD_SIZES, size))
+    return [size >> l for l in range(SWD_SIZES.index(size) + 1)]
+
+
+def _swd_mirror(idx, n):
+    idx = np.abs(idx)
+    return np.where(idx >= n, 2 * n - 2 - idx, idx)
+
+
+def _swd_filter(x, axis, taps):
+    """The 5 taps along ``axis`` with mirror border (scipy 'mirror', torch 'reflect'), t = 0 .. 4 in order."""
+    n = x.shape[axis]
+    out = np.zeros_like(x)
+    for t in range(5):
+        out = out + taps[t] * np.take(x, _swd_mirror(np.arange(n) + t - 2, n), axis=axis)
+    return out
+
+
+def swd_down(x):
+    x = np.asarray(x, dtype=np.float64)
+    return _swd_filter(_swd_filter(x, -1, SWD_TAPS)[..., ::2], -2, SWD_TAPS)[..., ::2, :]
+
+
+def swd_up(y):
+    y = np.asarray(y, dtype=np.float64)
+    rows = np.zeros(y.shape[:-2] + (2 * y.shape[-2], y.shape[-1]))
+    rows[..., ::2, :] = y
+    rows = _swd_filter(rows, -2, 2.0 * SWD_TAPS)
+    full = np.zeros(rows.shape[:-1] + (2 * y.shape[-1],))
+    full[..., ::2] = rows
+    return _swd_filter(full, -1, 2.0 * SWD_TAPS)
+
+
+def laplacian_pyramid(images):
+    """[N, C, S, S] -> the fp64 Laplacian levels of size S, S/2, .., 16: L_l = G_l - up(G_l+1), the last one G itself."""
+    g = np.asarray(images, dtype=np.float64)
+    if g.ndim != 4 or g.shape[2] != g.shape[3]:
+        raise ValueError("images must be [N, C, S, S], got %s" % (g.shape,))
+    levels = []
+    for _ in swd_level_sizes(g.shape[2])[:-1]:
+        nxt = swd_down(g)
+        levels.append(g - swd_up(nxt))
+        g = nxt
+    return levels + [g]
+
+
+def _swd_check_positions(pos, n, h):
+    pos = np.asarray(pos)
+    if pos.ndim != 3 or pos.shape[0] != n or pos.shape[2] != 2 or pos.shape[1] < 1:
+        raise ValueError("positions must be [n = %d, P >= 1, 2] patch centres, got %s" % (n, pos.shape))
+    if pos.min() < 3 or pos.max() >= h - 3:
+        raise ValueError("patch centres must lie in [3, %d)" % (h - 3))
+    return pos.astype(np.int64)
+
+
+def swd_descriptors(level, positions):
+    """[n, C, H, H] and centres [n, P, 2] (cy, cx) -> [n * P, 49 C]: row image * P + patch, element (channel, dy, dx)."""
+    level = np.asarray(level, dtype=np.float64)
+    n, c, h, _ = level.shape
+    pos = _swd_check_positions(positions, n, h)
+    off = np.arange(-3, 4)
+    ys = pos[:, :, 0, None, None, None] + off[None, None, None, :, None]
+    xs = pos[:, :, 1, None, None, None] + off[None, None, None, None, :]
+    d = level[np.arange(n)[:, None, None, None, None], np.arange(c)[None, None, :, None, None], ys, xs]
+    return d.reshape(n * pos.shape[1], c * SWD_PATCH * SWD_PATCH)
+
+
+def swd_channel_statistics(desc, channels):
+    """Mean and population standard deviation per channel over all values of a descriptor set, taken of v - v0 with v0
+    the channel's first value (the device does the same): a constant channel then has a deviation of exactly 0, whatever
+    its value -- summing n copies of it and dividing by n need not give it back."""
+    d = np.asarray(desc, dtype=np.float64).reshape(len(desc), channels, -1)
+    v0 = d[0, :, 0]
+    shifted = d - v0[None, :, None]
+    return v0 + shifted.mean(axis=(0, 2)), shifted.std(axis=(0, 2))
+
+
+def swd_normalise(desc, channels):
+    """(d - mean_c) / std_c per channel; a standard deviation of exactly 0 divides by 1 (a collapsed generator gets a
+    finite number, not NaN)."""
+    mean, std = swd_channel_statistics(desc, channels)
+    d = np.asarray(desc, dtype=np.float64).reshape(len(desc), channels, -1)
+    return ((d - mean[None, :, None]) / np.where(std == 0.0, 1.0, std)[None, :, None]).reshape(len(desc), -1)
+
+
+def sliced_wasserstein(desc_a, desc_b, directions, repeats=1):
+    """Two descriptor sets [rows, D] and unit directions [repeats * dirs, D]: every direction's projections of either set
+    sorted ascending; per repeat the mean over rows and directions of |a - b|; the mean over repeats."""
+    a, b = np.asarray(desc_a, dtype=np.float64), np.asarray(desc_b, dtype=np.float64)
+    dirs = np.asarray(directions, dtype=np.float64)
+    if a.shape != b.shape:
+        raise ValueError("the two sets must have equal shapes, got %s and %s" % (a.shape, b.shape))
+    if dirs.ndim != 2 or dirs.shape[1] != a.shape[1] or dirs.shape[0] % int(repeats):
+        raise ValueError("directions must be [repeats * dirs, %d], got %s" % (a.shape[1], dirs.shape))
+    pa, pb = np.sort(a.dot(dirs.T), axis=0), np.sort(b.dot(dirs.T), axis=0)
+    per = np.abs(pa - pb).reshape(a.shape[0], int(repeats), -1).mean(axis=(0, 2))
+    return float(per.mean())
+
+
+def _swd_result(sizes, values):
+    out = {"swd_%d" % s: float(v) for s, v in zip(sizes, values)}
+    out["swd"] = float(np.mean(values))
+    return out
+
+
+def swd(images_a, images_b, positions, directions, repeats=1):
+    """The whole statistic in numpy fp64.  ``positions[l]`` [n, P, 2] and ``directions[l]`` [repeats * dirs, 49 C] per
+    level (``SwdPlan`` draws them) -> {"swd_<size>": 1000 * distance per level, "swd": their mean}."""
+    la, lb = laplacian_pyramid(images_a), laplacian_pyramid(images_b)
+    channels, values = la[0].shape[1], []
+    for a, b, pos, dirs in zip(la, lb, positions, directions):
+        da, db = swd_normalise(swd_descriptors(a, pos), channels), swd_normalise(swd_descriptors(b, pos), channels)
+        values.append(1000.0 * sliced_wasserstein(da, db, dirs, repeats))
+    return _swd_result([a.shape[2] for a in la], values)
+
+
+class SwdPlan:
+    """Every draw of the metric, made once from a private ``numpy.random.Generator(PCG64(seed))``: per level the patch
+    centres [n, P, 2] (integers uniform in [3, H - 3), one table for both sets) and ``repeats * dirs`` unit directions
+    (standard normal, scaled to unit length in fp64, stored fp32); with ``module``, the latents of the generated set from
+    ``module.noise_distn`` under ``torch.random.fork_rng`` seeded from the same generator.  numpy's and torch's global
+    generators are left as they were.  The same draws every epoch keep the curve free of resampling noise."""
+
+    def __init__(self, size, channels, n_images, patches=128, dirs=128, repeats=4, seed=0, module=None):
+        self.size, self.channels, self.n = int(size), int(channels), int(n_images)
+        self.patches, self.dirs, self.repeats, self.seed = int(patches), int(dirs), int(repeats), int(seed)
+        self.sizes = swd_level_sizes(self.size)
+        if self.channels not in (1, 3) or min(self.n, self.patches, self.dirs, self.repeats) < 1:
+            raise ValueError("SwdPlan: channels must be 1 or 3 and every count at least 1")
+        rng = np.random.Generator(np.random.PCG64(self.seed))
+        self.positions = [rng.integers(3, h - 3, size=(self.n, self.patches, 2)).astype(np.int32) for h in self.sizes]
+        self.directions = []
+        for _ in self.sizes:
+            d = rng.standard_normal((self.repeats * self.dirs, SWD_PATCH * SWD_PATCH * self.channels))
+            self.directions.append((d / np.sqrt((d * d).sum(axis=1, keepdims=True))).astype(np.float32))
+        self.latents = None
+        if module is not None:
+            with torch.random.fork_rng(devices=[]):
+                torch.manual_seed(int(rng.integers(0, 2 ** 62)))
+                self.latents = module.noise_distn.sample((self.n, module.cfg.model.noise_dim))
+        self._device = {}
+
+    def on(self, device):
+        """(positions as int32 [n * P, 2], directions as fp32) per level on ``device``, uploaded once."""
+        key = str(device)
+        if key not in self._device:
+            self._device[key] = ([torch.from_numpy(p.reshape(-1, 2)).to(device) for p in self.positions],
+                                 [torch.from_numpy(d).to(device) for d in self.directions])
+        return self._device[key]
+
+
+def _swd_images(x, what):
+    if not isinstance(x, torch.Tensor) or not x.is_cuda:
+        raise RuntimeError("lightning_gan_zoo_amd.eval: the device %s runs on the HIP kernels; its input is not a GPU "
+                           "tensor and there is no fallback (use eval.swd)" % what)
+    if x.dim() != 4 or x.dtype != torch.float32 or x.shape[2] != x.shape[3] or x.shape[1] not in (1, 3):
+        raise ValueError("images must be float32 [N, C in (1, 3), S, S], got %s %s" % (x.dtype, tuple(x.shape)))
+    swd_level_sizes(x.shape[2])
+    return x if x.is_contiguous() else x.contiguous()
+
+
+def laplacian_pyramid_device(images):
+    """``laplacian_pyramid`` of fp32 device images [N, C, S, S]: one gz_swd_pyramid launch, the levels as views of one
+    packed fp32 buffer.  No CPU fallback."""
+    import ctypes
+    from . import functional as F
+    from ._lib import check, lib
+    x = _swd_images(images, "Laplacian pyramid")
+    n, c, s, _ = x.shape
+    count, offsets = ctypes.c_int(0), (ctypes.c_longlong * 5)()
+    check(lib.gz_swd_pyramid_describe(n, c, s, ctypes.byref(count), offsets), "swd_pyramid_describe")
+    with torch.cuda.device(x.device):
+        out = torch.empty((offsets[count.value],), dtype=torch.float32, device=x.device)
+        check(lib.gz_swd_pyramid(F._p(x), n, c, s, F._p(out), out.numel(), F._stream()), "swd_pyramid")
+    return [out[offsets[l]:offsets[l + 1]].view(n, c, s >> l, s >> l) for l in range(count.value)]
+
+
+def swd_sort_plan(rows):
+    """-> (block length, padded length, block passes, global passes) of gz_swd_sort_columns for ``rows`` keys a column."""
+    import ctypes
+    from ._lib import check, lib
+    block, padded, bp, gp = ctypes.c_int(0), ctypes.c_longlong(0), ctypes.c_int(0), ctypes.c_int(0)
+    check(lib.gz_swd_sort_plan(int(rows), ctypes.byref(block), ctypes.byref(padded), ctypes.byref(bp), ctypes.byref(gp)),
+          "swd_sort_plan")
+    return block.value, padded.value, bp.value, gp.value
+
+
+def swd_sorted_projections_device(level, pos, dirs):
+    """One level [n, C, H, H] (fp32, device), centres [n * P, 2] (int32, device) and directions [ndirs, 49 C] (fp32,
+    device) -> [ndirs, padded] fp32: every direction's projections of the normalised descriptors, sorted ascending, +inf
+    beyond the n * P rows.  gz_swd_channel_stats, gz_swd_project, gz_swd_sort_columns; nothing reaches the host."""
+    from . import functional as F
+    from ._lib import check, lib
+    level = _swd_images(level, "sorted projections")
+    n, c, h, _ = level.shape
+    for t, dtype, what in ((pos, torch.int32, "centres"), (dirs, torch.float32, "directions")):
+        if (not isinstance(t, torch.Tensor) or t.dtype != dtype or t.dim() != 2 or t.device != level.device
+                or not t.is_contiguous()):
+            raise ValueError("%s must be a contiguous 2-D %s tensor on %s (SwdPlan.on makes them)" % (what, dtype, level.device))
+    rows, ndirs = pos.shape[0], dirs.shape[0]
+    if pos.shape[1] != 2 or rows % n or rows < 1 or ndirs < 1 or dirs.shape[1] != SWD_PATCH * SWD_PATCH * c:
+        raise ValueError("centres must be [n * P, 2] and directions [ndirs, %d]" % (SWD_PATCH * SWD_PATCH * c))
+    p = rows // n
+    pitch = max(swd_sort_plan(rows)[1], 4)             # (the sort reads 16 bytes at a time)
+    with torch.cuda.device(level.device):
+        stats = torch.empty((2 * c,), dtype=torch.float64, device=level.device)
+        ws_bytes = lib.gz_swd_channel_stats_workspace_bytes(n, c, h, p)
+        ws = torch.empty(max(ws_bytes, 8), dtype=torch.uint8, device=level.device)
+        check(lib.gz_swd_channel_stats(F._p(level), n, c, h, F._p(pos), p, F._p(stats), F._p(ws), ws_bytes, F._stream()),
+              "swd_channel_stats")
+        proj = torch.empty((ndirs, pitch), dtype=torch.float32, device=level.device)
+        check(lib.gz_swd_project(F._p(level), n, c, h, F._p(pos), p, F._p(stats), F._p(dirs), ndirs, F._p(proj), pitch,
+                                 F._stream()), "swd_project")
+        check(lib.gz_swd_sort_columns(F._p(proj), rows, ndirs, pitch, F._stream()), "swd_sort_columns")
+    return proj
+
+
+def swd_distance_device(sorted_a, sorted_b, rows, repeats=1):
+    """Two results of ``swd_sorted_projections_device`` -> the mean over repeats of the mean |a - b| over rows and the
+    repeat's directions: gz_swd_distance, ``repeats`` doubles copied back."""
+    from . import functional as F
+    from ._lib import check, lib
+    if sorted_a.shape != sorted_b.shape or sorted_a.shape[0] % int(repeats):
+        raise ValueError("the two sets must have equal shapes with repeats * dirs directions, got %s and %s"
+                         % (tuple(sorted_a.shape), tuple(sorted_b.shape)))
+    per = sorted_a.shape[0] // int(repeats)
+    with torch.cuda.device(sorted_a.device):
+        out = torch.empty((int(repeats),), dtype=torch.float64, device=sorted_a.device)
+        ws_bytes = lib.gz_swd_distance_workspace_bytes(rows, per, int(repeats))
+        ws = torch.empty(max(ws_bytes, 8), dtype=torch.uint8, device=sorted_a.device)
+        check(lib.gz_swd_distance(F._p(sorted_a), rows, F._p(sorted_b), rows, per, int(repeats), sorted_a.shape[1],
+                                  F._p(out), F._p(ws), ws_bytes, F._stream()), "swd_distance")
+        sums = out.cpu().numpy()
+    return float((sums / (float(rows) * per)).mean())
+
+
+def sliced_wasserstein_device(level_a, level_b, pos, dirs, repeats=1, sorted_b=None):
+    """``sliced_wasserstein(swd_normalise(swd_descriptors(..)), ..)`` of two fp32 device levels with device centres and
+    directions.  ``sorted_b``: the second set's sorted projections when the caller keeps them.  No CPU fallback."""
+    for t in (level_a, level_b):
+        _swd_images(t, "sliced Wasserstein distance")
+    if level_a.shape != level_b.shape:
+        raise ValueError("the two sets must have equal shapes, got %s and %s" % (tuple(level_a.shape), tuple(level_b.shape)))
+    sa = swd_sorted_projections_device(level_a, pos, dirs)
+    sb = swd_sorted_projections_device(level_b, pos, dirs) if sorted_b is None else sorted_b
+    return swd_distance_device(sa, sb, pos.shape[0], repeats)
+
+
+class RealPyramid:
+    """The real set's side of the metric, made once per run: its Laplacian levels resident in fp32, and its sorted
+    projections per level, made at the first evaluation and kept while all levels' fit under ``cache_gb``; above the
+    budget they are recomputed from the resident levels at every evaluation (the same launches: the same bits)."""
+
+    def __init__(self, images, plan, cache_gb=16):
+        x = _swd_images(images, "sliced Wasserstein distance")
+        if tuple(x.shape) != (plan.n, plan.channels, plan.size, plan.size):
+            raise ValueError("the real set must be %s, got %s" % ((plan.n, plan.channels, plan.size, plan.size),
+                                                                  tuple(x.shape)))
+        self.plan, self.levels = plan, laplacian_pyramid_device(x)
+        padded = swd_sort_plan(plan.n * plan.patches)[1]
+        self.cache_bytes = len(self.levels) * plan.repeats * plan.dirs * padded * 4
+        self.cached = self.cache_bytes <= float(cache_gb) * 2 ** 30
+        self._sorted = {}
+
+    def sorted(self, l):
+        if l in self._sorted:
+            return self._sorted[l]
+        pos, dirs = self.plan.on(self.levels[l].device)
+        s = swd_sorted_projections_device(self.levels[l], pos[l], dirs[l])
+        if self.cached:
+            self._sorted[l] = s
+        return s
+
+
+def swd_device(images_a, images_b, positions, directions, repeats=1):
+    """``swd`` on fp32 device images: gz_swd_pyramid per set, then per level the statistics, projections, sorts and the
+    distance on the device; ``repeats`` doubles per level travel to the host.  ``positions`` / ``directions`` as for
+    ``swd`` (numpy; uploaded here).  No CPU fallback."""
+    a, b = _swd_images(images_a, "sliced Wasserstein distance"), _swd_images(images_b, "sliced Wasserstein distance")
+    if a.shape != b.shape or a.device != b.device:
+        raise ValueError("the two sets must have equal shapes on one device, got %s and %s" % (tuple(a.shape), tuple(b.shape)))
+    la, lb = laplacian_pyramid_device(a), laplacian_pyramid_device(b)
+    values = []
+    for x, y, pos, dirs in zip(la, lb, positions, directions):
+        pos = torch.from_numpy(np.ascontiguousarray(_swd_check_positions(pos, x.shape[0], x.shape[2]).reshape(-1, 2)
+                                                    .astype(np.int32))).to(a.device)
+        dirs = torch.from_numpy(np.ascontiguousarray(dirs, dtype=np.float32)).to(a.device)
+        values.append(1000.0 * sliced_wasserstein_device(x, y, pos, dirs, repeats))
+    return _swd_result([x.shape[2] for x in la], values)
+
+
+@torch.no_grad()
+def evaluate_swd(module, plan, real, batch=250):
+    """The metric of ``module.generator`` against ``real`` (a ``RealPyramid``): the eval-mode sweep over ``plan.latents``
+    -- the raw tanh output, not clamped -- the pyramid and per level one distance.  The module's mode, numpy's global
+    generator (a generator with ``sample_view`` draws from it: seeded from the plan's seed inside, restored afterwards)
+    and torch's generators are left as they were.  -> {"swd_<size>": .., "swd": mean}."""
+    from . import functional as F
+    if plan.latents is None:
+        raise ValueError("the plan was built without a module: it holds no latents")
+    gen = module.generator
+    if hasattr(gen, "drop_prefetched_view"):
+        # where the LIVE generator is swept (no averaging), its view prefetched for the next training step must be rolled
+        # back BEFORE numpy's state is saved: the sweep's forwards would otherwise discard it under the plan's seed without
+        # rolling back, and the next step would draw another view than a run without the metric.  (The averaged copy
+        # never holds one -- averaging.SCRATCH_ATTRS -- so there this does nothing and the live prefetch stays valid.)
+        gen.drop_prefetched_view()
+    host_state = np.random.get_state()
+    was_training = module.training
+    module.eval()
+    try:
+        np.random.seed(plan.seed % (2 ** 32))
+        with torch.random.fork_rng(devices=[module.device] if torch.device(module.device).type == "cuda" else []):
+            fake = torch.cat([F._req(module.generator(z.to(module.device)).detach().float(), "samples")
+                              for z in torch.split(plan.latents, int(batch))])
+    finally:
+        module.train(was_training)
+        np.random.set_state(host_state)
+    fake_levels = laplacian_pyramid_device(fake)
+    del fake
+    pos, dirs = plan.on(fake_levels[0].device)
+    values = []
+    for l, level in enumerate(fake_levels):
+        sorted_fake = swd_sorted_projections_device(level, pos[l], dirs[l])
+        values.append(1000.0 * swd_distance_device(sorted_fake, real.sorted(l), pos[l].shape[0], plan.repeats))
+    return _swd_result(plan.sizes, values)

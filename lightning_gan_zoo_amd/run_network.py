@@ -63,7 +63,14 @@ RUNNER_KEYS = {"max_steps": None, "log_every": 10, "dataset_path": None, "seed":
                "precision_recall": False, "precision_recall_k": 5,
                # DiffAugment of the discriminator's input (augment.py, csrc/gz_diffaug.hip): a comma-separated subset of
                # color, translation, cutout; "" = off.  Travels into the module's cfg as cfg.diffaugment
-               "diffaugment": ""}
+               "diffaugment": "",
+               # sliced Wasserstein distance on Laplacian-pyramid patches (eval.evaluate_swd, csrc/gz_swd.hip): a quality
+               # number per resolution level from pixels alone -- no network, no weight file.  swd_images real and as many
+               # generated images (clamped to the real images there are), swd_patches 7x7 patches per image and level,
+               # swd_repeats x swd_dirs directions, every draw from a private generator seeded with swd_seed; the real
+               # set's sorted projections stay resident while they fit under swd_cache_gb
+               "swd": False, "swd_images": 16384, "swd_patches": 128, "swd_dirs": 128, "swd_repeats": 4, "swd_seed": 0,
+               "swd_cache_gb": 16}
 BUILTIN_DATASETS = ("synthetic", "image_folder", "tensor_file", "celeb_a", "mnist")
 AVERAGE_PREFIX = "generator_average."     # state_dict keys of the averaged generator's parameters, next to generator.*
 LIGHTNING_VERSION_TAG = "1.2.0"       # envelope layout written below (Lightning 1.1 / 1.2 generation)
@@ -109,7 +116,27 @@ def check_diffaugment(run):
         raise SystemExit(str(e)) from e
 
 
+def check_swd_keys(run):
+    if not isinstance(run.get("swd", False), bool):
+        raise SystemExit("swd must be true or false, got %r" % (run["swd"],))
+    for key in ("swd_images", "swd_patches", "swd_dirs", "swd_repeats"):
+        v = run.get(key, 1)
+        if isinstance(v, bool) or not isinstance(v, int) or v < 1:
+            raise SystemExit("%s must be a positive integer, got %r" % (key, v))
+    seed = run.get("swd_seed", 0)
+    if isinstance(seed, bool) or not isinstance(seed, int) or seed < 0:
+        raise SystemExit("swd_seed must be a non-negative integer, got %r" % (seed,))
+    if run.get("swd", False) and run.get("resident_data", False):
+        raise SystemExit("swd=true is not served together with resident_data=true: the metric's real images come from "
+                         "the streaming loader's input step (or a synthetic set / tensor file), not from the resident "
+                         "set's gather; train without resident_data to score a run with swd")
+    gb = run.get("swd_cache_gb", 16)
+    if isinstance(gb, bool) or not isinstance(gb, (int, float)) or gb < 0:
+        raise SystemExit("swd_cache_gb must be a non-negative number, got %r" % (gb,))
+
+
 def check_eval_keys(run):
+    check_swd_keys(run)
     if run.get("fid_on_device", False) and not run.get("eval_on_device", False):
         raise SystemExit("fid_on_device=true is honoured only together with eval_on_device=true: the device Frechet "
                          "distance reads the moments the device evaluation pass leaves on the GPU")
@@ -520,11 +547,12 @@ class CheckpointKeeper:
 # the loop
 # ---------------------------------------------------------------------------------------------------------
 def fit(module, cfg, data, run, sync=None, rank=0, world=1, evaluate=None, slow_group=None, figures=None,
-        average=None):
+        average=None, monitor="fid"):
     """``pl.Trainer(max_epochs=cfg.train.num_epochs, resume_from_checkpoint=find_ckpt(...)).fit(model)`` for the
     step classes of this package (reference run_network.py:61-72).  ``figures``: an EpochFigures, drawn at every epoch
     end after the FID evaluation.  ``average``: an averaging.GeneratorAverage, advanced after every generator optimizer
-    step, saved in and restored from the checkpoints.  Returns (module, trainer, global_step)."""
+    step, saved in and restored from the checkpoints.  ``monitor``: the metric the best checkpoint is chosen by
+    (``checkpoint_monitor``).  Returns (module, trainer, global_step)."""
     from .harness import Trainer
     t = cfg.train
     # reference run_network.py:61-68: ``1`` or a ``{start_epoch, accumulation_factor}`` node -> Lightning's
@@ -538,7 +566,9 @@ def fit(module, cfg, data, run, sync=None, rank=0, world=1, evaluate=None, slow_
     step = epoch = 0
     skip = 0
     ckpt_dir = t.get("ckpt_dir")
-    keeper = CheckpointKeeper(ckpt_dir) if (ckpt_dir and cfg.get("save_ckpts", True)) else None
+    keeper = None
+    if ckpt_dir and cfg.get("save_ckpts", True):
+        keeper = CheckpointKeeper(ckpt_dir, monitor=monitor, filename="model_best-{%s:.2f}" % monitor)
     ckpt = find_ckpt(ckpt_dir)
     if ckpt:
         step, epoch, kst = load_checkpoint(ckpt, module, trainer, average, verbose=rank == 0)
@@ -740,8 +770,88 @@ def wants_fid(cfg, run):
                 and str(node.get("_target_", "")).endswith("ImageFolder"))
 
 
+def wants_evaluator(cfg, run):
+    """Rank 0 evaluates at every epoch end (FID, the sliced Wasserstein distance, or both) while the other ranks wait."""
+    return wants_fid(cfg, run) or bool(run.get("swd", False))
+
+
+def checkpoint_monitor(have_fid, run):
+    """The metric the best checkpoint is chosen by: FID wherever it is computed, else the sliced Wasserstein distance's
+    average over the levels when ``swd=true``, else (no metric) ``fid``, which is then never produced."""
+    return "swd" if (run.get("swd", False) and not have_fid) else "fid"
+
+
+def swd_real_images(cfg, run, data, device):
+    """The real set of the sliced Wasserstein distance: the first ``swd_images`` images in dataset order -- fewer where
+    the set has fewer -- as the training step sees them.  Dispatch follows ``build_data``: a synthetic set gives its one
+    batch, a tensor file its (already normalised) rows; an ImageFolder-shaped dataset gives the files of its validation
+    root where it has one, else of its training root, through the loader's own host half (``ImageFolderImages
+    .host_batches``: decode, resize) and the input step's device half (``functional.normalize_u8_images`` with
+    ``data_mean`` / ``data_std``), read once at start-up without the loader's prefetch thread.  The resident training
+    set is not served: ``swd=true`` with ``resident_data=true`` is refused by ``check_swd_keys``."""
+    from . import functional as F
+    t, want = cfg.train, int(run["swd_images"])
+    if isinstance(data, SyntheticImages):
+        return data.real[:want].float().contiguous()
+    if isinstance(data, TensorFileImages):
+        return data.data[:want].to(device).contiguous()
+    node = cfg.get("dataset") or {}
+    if not str(node.get("_target_", "")).endswith("ImageFolder"):
+        raise SystemExit("swd=true reads its real images from a synthetic set, a tensor file or an ImageFolder-shaped "
+                         "dataset; %r is none of them" % node.get("_target_"))
+    root = (node.get("val") or {}).get("root") or node.get("train", node)["root"]      # (train: as build_data finds it)
+    folder = ImageFolderImages(root, t.batch_size, t.img_size, t.channels_img, t.data_mean, t.data_std, device)
+    n, parts, have = min(want, len(folder.samples)), [], 0
+    for u8, _ in folder.host_batches():
+        parts.append(F.normalize_u8_images(torch.from_numpy(u8[:n - have]).to(device), t.data_mean, t.data_std))
+        have += len(parts[-1])
+        if have >= n:
+            break
+    return torch.cat(parts)
+
+
+class SwdScorer:
+    """The sliced Wasserstein distance as the runner evaluates it (eval.evaluate_swd).  ``load_real``, called once the
+    training data exist, takes the real images, draws the plan for their count -- patch centres, directions and the
+    generated set's latents, from a private generator seeded with ``swd_seed`` that leaves numpy's and torch's global
+    generators untouched, so a run with ``swd=true`` trains bit-identically to one without -- and makes the real set's
+    resident pyramid.  Calling it scores the module's current generator (inside ``rendering_from``: the averaged one)
+    -> {"swd_<size>": .., "swd": mean}."""
+
+    def __init__(self, cfg, run, module):
+        from . import eval as E
+        self.cfg, self.run, self.module, self.batch = cfg, run, module, int(run.get("eval_batch_size", 250))
+        self.sizes = E.swd_level_sizes(int(cfg.train.img_size))       # (a size the metric does not take ends the run here)
+        self.plan = self.real = None
+
+    def load_real(self, images):
+        from . import eval as E
+        t, run = self.cfg.train, self.run
+        self.plan = E.SwdPlan(int(t.img_size), int(t.channels_img), len(images), patches=run["swd_patches"],
+                              dirs=run["swd_dirs"], repeats=run["swd_repeats"], seed=run["swd_seed"], module=self.module)
+        self.real = E.RealPyramid(images, self.plan, cache_gb=run["swd_cache_gb"])
+
+    def __call__(self, module):
+        from . import eval as E
+        return E.evaluate_swd(module, self.plan, self.real, batch=self.batch)
+
+    def text(self, m):
+        return "SWD " + " ".join("%d: %.2f" % (s, m["swd_%d" % s]) for s in self.sizes) + " avg: %.2f" % m["swd"]
+
+
+def swd_evaluator(scorer, average=None):
+    """The ``evaluate`` hook of fit() of a run without an FID evaluator: the sliced Wasserstein distance alone."""
+    def evaluate(mod, epoch):
+        with rendering_from(mod, average):          # generator_average=true: the averaged generator is what is scored
+            m = scorer(mod)
+        print("epoch %d %s" % (epoch, scorer.text(m)))
+        return m
+
+    return evaluate
+
+
 def device_fid_evaluator(dump, features, real_act, device, batch=250, average=None, mu=None, sigma=None,
-                         fid_on_device=False, inception_score=False, inception_splits=10, prdc_k=None):
+                         fid_on_device=False, inception_score=False, inception_splits=10, prdc_k=None, swd=None):
     """The ``evaluate`` hook of fit() on the device pass (eval.evaluate_device).  The real set's device codes and its
     mean / covariance (``mu`` / ``sigma`` when a cache file holds them, else one moments launch) are made here, once per
     run; every epoch then costs the generated set alone.  ``fid_on_device``: the Frechet distance on the device as well
@@ -750,7 +860,8 @@ def device_fid_evaluator(dump, features, real_act, device, batch=250, average=No
     widened to fp64 on the device here, once per run; not the reference's torchvision network:
     eval.inception_score_from_logits); the best checkpoint stays chosen by FID.  ``prdc_k``: precision, recall, density
     and coverage over that many nearest neighbours as well (eval.prdc_device; the real set's radii are made by the first
-    evaluation and kept)."""
+    evaluation and kept).  ``swd``: a ``SwdScorer``; its numbers join the dict and the line, FID stays the monitored
+    metric."""
     from . import eval as E
     real = E.RealStatistics(real_act, device, mu=mu, sigma=sigma)
     extra = {"fid_on_device": True} if fid_on_device else {}
@@ -764,24 +875,28 @@ def device_fid_evaluator(dump, features, real_act, device, batch=250, average=No
     def evaluate(mod, epoch):
         with rendering_from(mod, average):          # generator_average=true: the averaged generator is what is scored
             m = E.evaluate_device(mod, dump, features.device, real, batch=batch, **extra)
+            if swd is not None:
+                m = dict(m, **swd(mod))
         line = "epoch %d FID: %.4f KID mean: %.6f KID stddev: %.6f" % (epoch, m["fid"], m["kid"], m["kid_std"])
         if inception_score:
             line += " IS: %.4f +- %.4f" % (m["is"], m["is_std"])
         if prdc_k is not None:
             line += " P: %.4f R: %.4f D: %.4f C: %.4f" % (m["precision"], m["recall"], m["density"], m["coverage"])
+        if swd is not None:
+            line += " " + swd.text(m)
         print(line)
         return m
 
     return evaluate
 
 
-def make_fid_evaluator(cfg, run, module, device, average=None):
+def make_fid_evaluator(cfg, run, module, device, average=None, swd=None):
     """The reference's InceptionMetrics callback (run_network.py:51-56, core/callback_inception_metrics.py:136-246) as
     the ``evaluate`` hook of fit(): FID / KID of ``val.fid_n_samples`` generated images against the validation images,
     both through the InceptionV3 pool features on the HIP kernels (inception.py).  Needs the FID weight file the
     reference downloads (``inception_weights=<path to pt_inception-2015-12-05-6726825d.pth>``; no network here) and an
     ImageFolder-shaped validation set; returns None otherwise, and the run keeps its latest checkpoint instead of
-    the best-FID one."""
+    the best-FID one.  ``swd``: a ``SwdScorer`` whose numbers join every evaluation's dict and line."""
     node = cfg.get("dataset") or {}
     if not (cfg.get("calc_fid", True) and run.get("inception_weights")):
         return None
@@ -808,7 +923,8 @@ def make_fid_evaluator(cfg, run, module, device, average=None):
             score["prdc_k"] = int(run.get("precision_recall_k", 5))
         return device_fid_evaluator(dump, features, real_act, device, batch=int(run.get("eval_batch_size", 250)),
                                     average=average, mu=mu, sigma=sigma,
-                                    fid_on_device=bool(run.get("fid_on_device", False)), **score)
+                                    fid_on_device=bool(run.get("fid_on_device", False)),
+                                    **(dict(score, swd=swd) if swd is not None else score))
     kid_on_device = bool(run.get("kid_on_device", False))
     # real_act is the same every epoch: its fp64 device copy is made once per run, here
     real_codes = E.device_codes(real_act, device) if kid_on_device else None
@@ -817,7 +933,10 @@ def make_fid_evaluator(cfg, run, module, device, average=None):
         with rendering_from(mod, average):          # generator_average=true: the averaged generator is what is scored
             m = E.evaluate(mod, dump, features, real_act, kid_on_device=kid_on_device,
                            real_codes_device=real_codes)
-        print("epoch %d FID: %.4f KID mean: %.6f KID stddev: %.6f" % (epoch, m["fid"], m["kid"], m["kid_std"]))
+            if swd is not None:
+                m = dict(m, **swd(mod))
+        print("epoch %d FID: %.4f KID mean: %.6f KID stddev: %.6f" % (epoch, m["fid"], m["kid"], m["kid_std"])
+              + ("" if swd is None else " " + swd.text(m)))
         return m
 
     return evaluate
@@ -860,32 +979,37 @@ def main(argv=None):
     if world > 1:
         from .ddp import GradSync
         sync = GradSync(module)
-        if wants_fid(cfg, run):
+        if wants_evaluator(cfg, run):
             # with the FID evaluator on, rank 0 alone generates val.fid_n_samples images and runs InceptionV3 over them
             # at start-up and at every epoch end -- far longer than the default watchdog's 10 minutes.  Only THOSE waits
             # get a long timeout (their own group); every training collective keeps the default, so a rank that dies
-            # mid-training is still noticed in minutes.
+            # mid-training is still noticed in minutes.  (swd=true: the same wait, for rank 0's sweep, sorts and distances.)
             import datetime
             # (gloo: the wait is a host-side one, no GPU stream sits behind it)
             slow_group = torch.distributed.new_group(timeout=datetime.timedelta(hours=6), backend="gloo")
-    evaluate, failure = None, None
+    evaluate, failure, scorer = None, None, None
     if rank == 0:
         try:
-            evaluate = make_fid_evaluator(cfg, run, module, device, average)
+            if run["swd"]:
+                scorer = SwdScorer(cfg, run, module)
+            evaluate = make_fid_evaluator(cfg, run, module, device, average, swd=scorer)
         except BaseException as e:  # noqa: BLE001  (SystemExit from a missing weight file included)
             failure = e
             if slow_group is None:
                 raise
-    if slow_group is not None:
-        # rank 0 has the real activations (computed or loaded) before step 0 -- or failed, and then says so: the
-        # other ranks leave with it instead of sitting in a barrier for the long timeout
+    def leave_together(failure):
+        # rank 0 has what its evaluator needs before step 0 -- or failed, and then says so: the other ranks leave with
+        # it instead of sitting in a barrier for the long timeout
         flag = torch.tensor([1 if failure is not None else 0])
         torch.distributed.broadcast(flag, 0, group=slow_group)
         if int(flag.item()):
             if rank == 0:
-                print("FID evaluator could not be built on rank 0: %r" % (failure,), file=sys.stderr)
+                print("the evaluator could not be built on rank 0: %r" % (failure,), file=sys.stderr)
             torch.distributed.destroy_process_group()
             raise SystemExit(2)
+
+    if slow_group is not None:
+        leave_together(failure)
     figures = None
     if run["figures"]:
         from .core.figures.types import build_figures
@@ -893,8 +1017,8 @@ def main(argv=None):
             figs = build_figures(cfg, module, module.logging_dir)
         except ValueError as e:
             raise SystemExit("figures: %s" % e) from e
-        figures = EpochFigures(figs, have_fid=evaluate is not None or slow_group is not None, rank=rank, world=world,
-                               group=slow_group, average=average)
+        have_fid = evaluate is not None or (world > 1 and wants_fid(cfg, run))      # (the SWD hook is made further down)
+        figures = EpochFigures(figs, have_fid=have_fid, rank=rank, world=world, group=slow_group, average=average)
     data_group = slow_group
     if world > 1 and run["resident_data"] and data_group is None:
         # rank 0 decodes the whole training set once while the others wait for its cache file: the same kind of
@@ -902,8 +1026,24 @@ def main(argv=None):
         import datetime
         data_group = torch.distributed.new_group(timeout=datetime.timedelta(hours=6), backend="gloo")
     data = build_data(cfg, run, device, rank, world, group=data_group)
+    monitor = checkpoint_monitor(evaluate is not None, run)
+    if run["swd"]:
+        # the real set needs the training data, so it is made here: rank 0 reads it while the others wait on the
+        # long-timeout group, and a failure is told to them as above
+        failure = None
+        if scorer is not None:
+            try:
+                scorer.load_real(swd_real_images(cfg, run, data, device))
+            except BaseException as e:  # noqa: BLE001
+                failure = e
+                if slow_group is None:
+                    raise
+            if evaluate is None:
+                evaluate = swd_evaluator(scorer, average)
+        if slow_group is not None:
+            leave_together(failure)
     out = fit(module, cfg, data, run, sync=sync, rank=rank, world=world, evaluate=evaluate, slow_group=slow_group,
-              figures=figures, average=average)
+              figures=figures, average=average, monitor=monitor)
     if world > 1:
         torch.distributed.destroy_process_group()
     return out
