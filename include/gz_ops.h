@@ -275,6 +275,12 @@ int gz_conv2d_fwd_any_into(const float* x, const float* wpack, const float* bias
  * network's patched pools), 2 average over KS*KS.  nn.AdaptiveAvgPool2d(1) = KS = H, S = 1, P = 0, mode 2. */
 int gz_pool2d(const float* x, float* y, long long planes, int H, int W, int OH, int OW, int KS, int S, int P, int mode,
               hipStream_t stream);
+/* The launch gz_pool2d makes for these arguments, as one line of text: "global_avg<16> grid=..", "band<3,2> grid=..
+ * lds=..", "group<3,1,1> G=.. grid=.. lds=..", "group<3,2,0> ..", "plane grid=.. lds=..", "flat grid=..".  Host only (no
+ * HIP call, no GPU needed); launcher and text read one choice.  x_aligned16: whether x is 16-byte aligned.  knobs: -1
+ * the switches of this process, otherwise bit 0 = GZ_NO_POOL_GROUP, bit 1 = GZ_NO_POOL_PLANE.  Returns the length. */
+int gz_pool2d_plan(long long planes, int H, int W, int OH, int OW, int KS, int S, int P, int mode, int x_aligned16,
+                   int knobs, char* buf, int buflen);
 /* y = F.interpolate(x, (OH, OW), mode='bilinear', align_corners=False) * mul + add */
 int gz_resize_bilinear(const float* x, float* y, long long planes, int H, int W, int OH, int OW, float mul, float add,
                        hipStream_t stream);

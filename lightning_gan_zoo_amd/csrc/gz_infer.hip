@@ -1,6 +1,8 @@
 // Evaluation-path helpers (the InceptionV3 feature extractor behind FID / KID, reference
 // core/callback_inception_metrics.py:183-246, core/submodules/gan_stability/metrics/inception.py): 2-D pooling,
 // bilinear resize, generator output -> Inception input.  One lane per output element, lanes along the row; forward only.
+#include <stdio.h>
+
 #include "gz_common.h"
 #include "gz_knobs.h"
 #include "../../include/gz_ops.h"
@@ -181,15 +183,70 @@ __global__ __launch_bounds__(IT) void global_avg_kernel(const float* __restrict_
     if (unit < planes && sub == 0) y[unit] = acc * inv;
 }
 
+// Which kernel a pooling launch takes, with the launch parameters that follow from the shape: decided once, by
+// choose_pool; gz_pool2d switches on the answer and gz_pool2d_plan prints it.  Plain host arithmetic.
+enum PoolKind { PoolGlobalAvg, PoolBand, PoolGroup311, PoolGroup320, PoolPlane, PoolFlat };
+
+struct PoolChoice {
+    PoolKind kind;
+    int G;          // group kernels: planes per LDS image group
+    int grid;       // workgroups
+    size_t lds;     // dynamic LDS bytes (0: none)
+};
+
+constexpr int POOL_BAND_ROWS = 8;     // output rows per workgroup of the band kernel
+
+static int infer_grid(long long items) {
+    long long b = (items + IT - 1) / IT;
+    if (b > 256 * 16) b = 256 * 16;
+    return (int)(b < 1 ? 1 : b);
+}
+
+// `planes`, H, W, OH, OW, KS, S, P, mode as gz_pool2d has validated them; x_aligned16: x is 16-byte aligned
+static PoolChoice choose_pool(long long planes, int H, int W, int OH, int OW, int KS, int S, int P, int mode,
+                              bool x_aligned16, bool no_pool_group, bool no_pool_plane) {
+    PoolChoice c{PoolFlat, 0, 0, 0};
+    if (KS == H && KS == W && P == 0 && mode != 0 && H * W == 64 && planes < (1ll << 31) / 16 && x_aligned16 &&
+        !no_pool_group) {
+        const long long threads = planes * 16;
+        c.kind = PoolGlobalAvg;
+        c.grid = (int)((threads + IT - 1) / IT);
+        return c;
+    }
+    if (KS == 3 && S == 2 && P == 0 && H * W > 8192 && W <= 1024 && planes * 64 < (1ll << 31) && !no_pool_group) {
+        const int OB = POOL_BAND_ROWS, bands = (OH + OB - 1) / OB;
+        c.kind = PoolBand;
+        c.lds = (size_t)((OB - 1) * S + KS) * W * 4;
+        c.grid = (int)(unsigned)(planes * bands);
+        return c;
+    }
+    if (KS == 3 && H >= 3 && W >= 3 && H * W <= 8192 && planes < (1ll << 31) && !no_pool_plane && !no_pool_group &&
+        ((S == 1 && P == 1) || (S == 2 && P == 0))) {
+        const int hw = H * W, PS = (H + 2 * P) * (W + 2 * P);
+        int G = 2048 / hw;
+        G = G < 1 ? 1 : G;
+        const int groups = (int)((planes + G - 1) / G);
+        c.kind = S == 1 ? PoolGroup311 : PoolGroup320;
+        c.G = G;
+        c.grid = groups < 8192 ? groups : 8192;
+        c.lds = (size_t)G * PS * 4;
+        return c;
+    }
+    if (H * W <= 8192 && planes < (1ll << 31) && !no_pool_plane) {
+        c.kind = PoolPlane;
+        c.grid = (int)(planes < 65536 ? planes : 65536);
+        c.lds = (size_t)H * W * 4;
+        return c;
+    }
+    c.grid = infer_grid(planes * OH * OW);
+    return c;
+}
+
 template <int KS, int S, int P>
-static void launch_pool_group(const float* x, float* y, int planes, int H, int W, int OH, int OW, int mode,
-                              hipStream_t stream) {
-    const int hw = H * W, PS = (H + 2 * P) * (W + 2 * P);
-    int G = 2048 / hw;
-    G = G < 1 ? 1 : G;
-    const int groups = (planes + G - 1) / G;
-    const int grid = groups < 8192 ? groups : 8192;
-    const size_t lds = (size_t)G * PS * 4;
+static void launch_pool_group(const PoolChoice& pc, const float* x, float* y, int planes, int H, int W, int OH, int OW,
+                              int mode, hipStream_t stream) {
+    const int hw = H * W, G = pc.G, grid = pc.grid;
+    const size_t lds = pc.lds;
     const gz::FastDiv a = gz::make_fastdiv(hw), b = gz::make_fastdiv(W), c = gz::make_fastdiv(OH * OW),
                       d = gz::make_fastdiv(OW);
     if (mode == 0)
@@ -283,59 +340,76 @@ __global__ __launch_bounds__(IT) void samples_to_inception_kernel(const float* _
     }
 }
 
-static int infer_grid(long long items) {
-    long long b = (items + IT - 1) / IT;
-    if (b > 256 * 16) b = 256 * 16;
-    return (int)(b < 1 ? 1 : b);
-}
-
 }  // namespace gz
 
 using namespace gz;
 
 extern "C" {
 
+static int pool_args_ok(long long planes, int H, int W, int OH, int OW, int KS, int S, int P, int mode) {
+    if (planes <= 0 || H <= 0 || W <= 0 || KS <= 0 || S <= 0 || P < 0 || mode < 0 || mode > 2) return 0;
+    if (OH != (H + 2 * P - KS) / S + 1 || OW != (W + 2 * P - KS) / S + 1 || OH <= 0 || OW <= 0) return 0;
+    return 1;
+}
+
 int gz_pool2d(const float* x, float* y, long long planes, int H, int W, int OH, int OW, int KS, int S, int P, int mode,
               hipStream_t stream) {
     gz::clear_stale_error();
-    if (planes <= 0 || H <= 0 || W <= 0 || KS <= 0 || S <= 0 || P < 0 || mode < 0 || mode > 2) return GZ_ERR_BAD_SHAPE;
-    if (OH != (H + 2 * P - KS) / S + 1 || OW != (W + 2 * P - KS) / S + 1 || OH <= 0 || OW <= 0) return GZ_ERR_BAD_SHAPE;
-    const long long total = planes * OH * OW;
-    if (KS == H && KS == W && P == 0 && mode != 0 && H * W == 64 && planes < (1ll << 31) / 16 && !((uintptr_t)x & 15) &&
-        !gz::knobs().no_pool_group) {
-        const long long threads = planes * 16;
-        hipLaunchKernelGGL((global_avg_kernel<16>), dim3((unsigned)((threads + IT - 1) / IT)), dim3(IT), 0, stream, x, y,
-                           (int)planes, 1.f / 64.f);
-        return launch_status();
+    if (!pool_args_ok(planes, H, W, OH, OW, KS, S, P, mode)) return GZ_ERR_BAD_SHAPE;
+    const PoolChoice c = choose_pool(planes, H, W, OH, OW, KS, S, P, mode, !((uintptr_t)x & 15),
+                                     gz::knobs().no_pool_group, gz::knobs().no_pool_plane);
+    switch (c.kind) {
+        case PoolGlobalAvg:
+            hipLaunchKernelGGL((global_avg_kernel<16>), dim3((unsigned)c.grid), dim3(IT), 0, stream, x, y, (int)planes,
+                               1.f / 64.f);
+            break;
+        case PoolBand: {
+            const int OB = POOL_BAND_ROWS, bands = (OH + OB - 1) / OB;
+            const gz::FastDiv a = gz::make_fastdiv(bands), b = gz::make_fastdiv(OW);
+            if (mode == 0)
+                hipLaunchKernelGGL((pool2d_band_kernel<3, 2, 0>), dim3((unsigned)c.grid), dim3(IT), c.lds, stream, x, y, H, W,
+                                   OH, OW, OB, bands, a, b);
+            else
+                hipLaunchKernelGGL((pool2d_band_kernel<3, 2, 2>), dim3((unsigned)c.grid), dim3(IT), c.lds, stream, x, y, H, W,
+                                   OH, OW, OB, bands, a, b);
+            break;
+        }
+        case PoolGroup311:
+            launch_pool_group<3, 1, 1>(c, x, y, (int)planes, H, W, OH, OW, mode, stream);
+            break;
+        case PoolGroup320:
+            launch_pool_group<3, 2, 0>(c, x, y, (int)planes, H, W, OH, OW, mode, stream);
+            break;
+        case PoolPlane:
+            hipLaunchKernelGGL(pool2d_plane_kernel, dim3(c.grid), dim3(IT), c.lds, stream, x, y, (int)planes, H, W, OH, OW, KS,
+                               S, P, mode, gz::make_fastdiv(OW));
+            break;
+        case PoolFlat:
+            hipLaunchKernelGGL(pool2d_kernel, dim3(c.grid), dim3(IT), 0, stream, x, y, planes * OH * OW, H, W, OH, OW, KS, S,
+                               P, mode);
+            break;
     }
-    if (KS == 3 && S == 2 && P == 0 && H * W > 8192 && W <= 1024 && planes * 64 < (1ll << 31) && !gz::knobs().no_pool_group) {
-        const int OB = 8, bands = (OH + OB - 1) / OB;
-        const size_t lds = (size_t)((OB - 1) * S + KS) * W * 4;
-        const gz::FastDiv a = gz::make_fastdiv(bands), b = gz::make_fastdiv(OW);
-        const unsigned grid = (unsigned)(planes * bands);
-        if (mode == 0)
-            hipLaunchKernelGGL((pool2d_band_kernel<3, 2, 0>), dim3(grid), dim3(IT), lds, stream, x, y, H, W, OH, OW, OB, bands,
-                               a, b);
-        else
-            hipLaunchKernelGGL((pool2d_band_kernel<3, 2, 2>), dim3(grid), dim3(IT), lds, stream, x, y, H, W, OH, OW, OB, bands,
-                               a, b);
-        return launch_status();
-    }
-    if (KS == 3 && H >= 3 && W >= 3 && H * W <= 8192 && planes < (1ll << 31) && !gz::knobs().no_pool_plane &&
-        !gz::knobs().no_pool_group && ((S == 1 && P == 1) || (S == 2 && P == 0))) {
-        if (S == 1) launch_pool_group<3, 1, 1>(x, y, (int)planes, H, W, OH, OW, mode, stream);
-        else launch_pool_group<3, 2, 0>(x, y, (int)planes, H, W, OH, OW, mode, stream);
-        return launch_status();
-    }
-    if (H * W <= 8192 && planes < (1ll << 31) && !gz::knobs().no_pool_plane) {
-        const int grid = (int)(planes < 65536 ? planes : 65536);
-        hipLaunchKernelGGL(pool2d_plane_kernel, dim3(grid), dim3(IT), (size_t)H * W * 4, stream, x, y, (int)planes, H, W, OH,
-                           OW, KS, S, P, mode, gz::make_fastdiv(OW));
-        return launch_status();
-    }
-    hipLaunchKernelGGL(pool2d_kernel, dim3(infer_grid(total)), dim3(IT), 0, stream, x, y, total, H, W, OH, OW, KS, S, P,
-                       mode);
     return launch_status();
+}
+
+/* The launch gz_pool2d makes for these arguments, as text (host only, no HIP call).  x_aligned16: whether x is 16-byte
+ * aligned; knobs: -1 this process's own switches, otherwise bit 0 = no_pool_group, bit 1 = no_pool_plane. */
+int gz_pool2d_plan(long long planes, int H, int W, int OH, int OW, int KS, int S, int P, int mode, int x_aligned16,
+                   int knobs, char* buf, int buflen) {
+    if (!buf || buflen <= 0) return GZ_ERR_BAD_SHAPE;
+    buf[0] = 0;
+    if (!pool_args_ok(planes, H, W, OH, OW, KS, S, P, mode) || knobs < -1 || knobs > 3) return GZ_ERR_BAD_SHAPE;
+    const bool no_group = knobs < 0 ? gz::knobs().no_pool_group : (knobs & 1) != 0;
+    const bool no_plane = knobs < 0 ? gz::knobs().no_pool_plane : (knobs & 2) != 0;
+    const PoolChoice c = choose_pool(planes, H, W, OH, OW, KS, S, P, mode, x_aligned16 != 0, no_group, no_plane);
+    switch (c.kind) {
+        case PoolGlobalAvg: return snprintf(buf, (size_t)buflen, "global_avg<16> grid=%d", c.grid);
+        case PoolBand: return snprintf(buf, (size_t)buflen, "band<3,2> grid=%d lds=%zu", c.grid, c.lds);
+        case PoolGroup311: return snprintf(buf, (size_t)buflen, "group<3,1,1> G=%d grid=%d lds=%zu", c.G, c.grid, c.lds);
+        case PoolGroup320: return snprintf(buf, (size_t)buflen, "group<3,2,0> G=%d grid=%d lds=%zu", c.G, c.grid, c.lds);
+        case PoolPlane: return snprintf(buf, (size_t)buflen, "plane grid=%d lds=%zu", c.grid, c.lds);
+        default: return snprintf(buf, (size_t)buflen, "flat grid=%d", c.grid);
+    }
 }
 
 int gz_resize_bilinear(const float* x, float* y, long long planes, int H, int W, int OH, int OW, float mul, float add,
