@@ -22,8 +22,10 @@ INCLUDE = os.path.join(os.path.dirname(HERE), "include")
 LIB_PATH = os.path.join(CSRC, "libgz_hip.so")
 ARCH = "gfx950"
 DIGEST_SOURCE = "gz_build_id.hip"          # holds gz_source_digest(); compiled with -DGZ_SOURCE_DIGEST=...
-# (longest compile first: the pool takes the list in order, and gz_conv.hip alone is most of a build's wall time)
-SOURCES = ["gz_conv.hip", "gz_conv3d.hip", "gz_conv_direct.hip", "gz_pack.hip", "gz_norm.hip", "gz_misc.hip", "gz_resample.hip", "gz_optim.hip",
+# (longest compile first, as measured one unit at a time: the pool takes the list in order, and the conv2d launcher
+# units -- one per op, F in two by skeleton -- are the build's critical path; DESIGN.md section 4 has the figures)
+SOURCES = ["gz_conv_fwd.hip", "gz_conv_dgrad.hip", "gz_conv_wgrad.hip", "gz_conv3d.hip", "gz_conv_direct.hip",
+           "gz_conv_fwd_igemm.hip", "gz_conv.hip", "gz_pack.hip", "gz_norm.hip", "gz_misc.hip", "gz_resample.hip", "gz_optim.hip",
            "gz_resnet.hip", "gz_loss.hip", "gz_infer.hip", "gz_figures.hip", "gz_ema.hip", "gz_kid.hip", "gz_moments.hip",
            "gz_sqrtm.hip", "gz_inception_score.hip", "gz_prdc.hip", "gz_diffaug.hip", "gz_swd.hip"]
 FLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-I", INCLUDE]

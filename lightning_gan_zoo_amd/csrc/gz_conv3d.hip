@@ -2,7 +2,7 @@
 // HoloGAN's ConvTranspose3d(k3, s2, p1, output_padding 1) forward (= Dg), its input gradient (= F)
 // and weight gradient (= Wg).  Reference call sites: core/models/hologan_generator.py:29-30,55-58.
 //
-// As in gz_conv.hip, one function per op -- choose_fwd3 / choose_dgrad3 / choose_wgrad3 -- decides skeleton, loader,
+// As for conv2d (gz_conv2d_choose.h), one function per op -- choose_fwd3 / choose_dgrad3 / choose_wgrad3 -- decides skeleton, loader,
 // tile and splits once (gz_conv_choice.h): launch_*3 switch on the answer, gz_conv3d_*_workspace_bytes size its slabs,
 // gz_conv3d_plan prints it.
 #include <cstdio>
@@ -276,7 +276,7 @@ static TileId pick3(long long M, long long N, int ny) {
     return T64x64;
 }
 
-// split-K of under-filled F / Dg launches: same policy as gz_conv.hip (plan_split)
+// split-K of under-filled F / Dg launches: same policy as conv2d (plan_split, gz_conv2d_choose.h)
 static int plan3(TileId tile, long long M, long long N, int Kdim, int ny) {
     const long long tiles = tiles3(tile, M, N, ny);
     const int chunks = (Kdim + BK - 1) / BK;

@@ -1,4 +1,4 @@
-// The vocabulary of a launch choice, shared by gz_conv.hip (conv2d), its direct kernels (gz_conv_direct.hip) and
+// The vocabulary of a launch choice, shared by conv2d (gz_conv2d_choose.h and the units that read it), its direct kernels (gz_conv_direct.hip) and
 // gz_conv3d.hip (conv3d): tile ids, skeleton kinds, loaders, the facts only a call knows, and the Choice the choose_*
 // functions of both dispatchers return.  choose_* answers "which kernel does this launch take" once per op: launch_*
 // switch on the answer, the workspace sizes are read from it, gz_conv2d_plan / gz_conv3d_plan print it.  Plain host

@@ -1,4 +1,4 @@
-// What the conv2d dispatcher (gz_conv.hip) calls of the direct kernels (gz_conv_direct.hip): per family the predicate that
+// What the conv2d dispatcher (choose_*: gz_conv2d_choose.h; launch_*: gz_conv_{fwd,dgrad,wgrad}.hip) calls of the direct kernels (gz_conv_direct.hip): per family the predicate that
 // admits a shape, the sizing helper whose answer goes into the Choice or the workspace size, and the launcher.  The
 // kernels, their templates and the switches over their template parameters stay on the other side.
 #pragma once

@@ -1,6 +1,6 @@
 // The direct (non-implicit-GEMM) convolution kernels: six families for layers an MFMA tile of the igemm skeletons would
 // mostly pad -- <= 4 image channels, or <= 32 channels on both sides of a 3x3 -- each with the predicate that admits a
-// shape, its block-count helper and its launcher.  choose_* / launch_* of gz_conv.hip decide when one is taken and reach
+// shape, its block-count helper and its launcher.  choose_* (gz_conv2d_choose.h) decide when one is taken, launch_* (gz_conv_{fwd,dgrad,wgrad}.hip) reach
 // this file through gz_conv_direct.h only; the weight images they read are gz_pack.hip's.
 //
 //   Dg  dgrad_smallc_k4s2p1 / dgrad_smallc4_k4s2p1 (k4 s2 p1 and 5x5 s2 p2 onto <= 4 channels)

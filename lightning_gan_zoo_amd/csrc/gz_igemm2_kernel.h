@@ -485,6 +485,9 @@ inline int launch_igemm2(const typename AL::Params& pa, const typename BL::Param
     g.gm.stagger = (Cfg::OCC == 2 && g.nz == 1 && g.grid.x >= 1536)
                        ? (int)((long long)g.gm.chunks * 8 * Cfg::TM * Cfg::TN * 64 * 2 * stagger_pct / 100) : 0;
     bool kg2 = false, ok = false;
+#ifdef GZ2_STAMPS
+    gz2_last_stamps() = HIP_SYMBOL(gz2_stamps);      // (this unit's copy of the array)
+#endif
     if constexpr (igemm2_kg2_built<Cfg, AL>()) {
         kg2 = igemm2_use_kg2((long long)g.grid.x * g.nz, g.gm.chunks_per_split);
         if (kg2)

@@ -67,6 +67,12 @@ constexpr bool GZ2_STEP = false;
 // z-slab with blockIdx.x < 64 writes them: the last writer stays -- fine for a diagnostic of grids of a few hundred.)
 #ifdef GZ2_STAMPS
 __device__ unsigned long long gz2_stamps[8192 * 8];
+// (a device array per unit that includes this header: launch_igemm2 notes here which unit's array its kernel writes, and
+// gz_debug_read_stamps reads that one -- the stamps of the last igemm2 launch, whichever unit launched it)
+inline const void*& gz2_last_stamps() {
+    static const void* last = nullptr;
+    return last;
+}
 template <int STEPS>
 struct Igemm2Probe {
     static constexpr bool STEP = GZ2_STEP;

@@ -363,7 +363,7 @@ struct EpiNCHWB {
 };
 
 // The lean NCHW store WITH per-channel bias and ReLU (round 6: the evaluation path -- BatchNorm folded into weights +
-// bias, then ReLU; csrc/gz_conv.hip run_fwd_any2).  A type of its own: adding bias / activation to EpiNCHWB's fast path
+// bias, then ReLU; csrc/gz_conv_fwd.hip run_fwd_any2).  A type of its own: adding bias / activation to EpiNCHWB's fast path
 // made EVERY igemm2 instantiation spill (round 4).  Channel blocks outside the tensor take EpiNCHW's element-wise path.
 struct EpiNCHWBiasAct {
     static constexpr bool SWAP = true;

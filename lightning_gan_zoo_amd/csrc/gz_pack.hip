@@ -1,5 +1,5 @@
 // What runs around the convolution launches of a step, on their weights: the packers that turn a weight tensor into
-// the [k][mn] images the launchers of gz_conv.hip / gz_conv_direct.hip read (gz_conv2d_pack_*; the layout rules both
+// the [k][mn] images the launchers of gz_conv_{fwd,dgrad,wgrad}.hip / gz_conv_direct.hip read (gz_conv2d_pack_*; the layout rules both
 // sides must agree on are in gz_pack_layout.h), and the sums of the weight-gradient slabs a split launch leaves behind
 // (launch_reduce_*: per launch; gz_reduce_multi: one launch for many gradients).  No kernel here uses the implicit-GEMM
 // skeletons.

@@ -1,5 +1,5 @@
 // The layout of the packed weight images: what the packers (gz_pack.hip) write and what the launchers that read them
-// (gz_conv.hip, gz_conv_direct.hip, the loaders of gz_igemm_loaders.h) must agree on -- the reduction chunk the images
+// (gz_conv_{fwd,dgrad,wgrad}.hip, gz_conv_direct.hip, the loaders of gz_igemm_loaders.h) must agree on -- the reduction chunk the images
 // are padded to, the taps of a transposed convolution's phase, and the rules that make an image tap-major.
 #pragma once
 #include "gz_common.h"

@@ -6,7 +6,7 @@
 // w+4, ... of source 0, then of source 1, ... (four independent accumulators per lane), the four partial sums meet in LDS
 // in wavefront order.  The result is valid in wavefront 0.
 //
-// Host side (below): the per-launch slab sums a split weight-gradient launch of gz_conv.hip or gz_conv_direct.hip ends
+// Host side (below): the per-launch slab sums a split weight-gradient launch of gz_conv_wgrad.hip or gz_conv_direct.hip ends
 // with (kernels in gz_pack.hip), and how gz_conv2d_wgrad_partial / gz_conv2d_wgrad_act_partial ask for them to be left out.
 #pragma once
 #include "gz_common.h"

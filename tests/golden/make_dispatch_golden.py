@@ -4,7 +4,7 @@ without a GPU).
 
     python tests/golden/make_dispatch_golden.py            # regenerate after a DELIBERATE heuristic change
 
-tests/test_dispatch_plan.py compares the library against this table, so an edit of a threshold in csrc/gz_conv.hip,
+tests/test_dispatch_plan.py compares the library against this table, so an edit of a threshold in csrc/gz_conv2d_choose.h,
 csrc/gz_conv_direct.hip or csrc/gz_conv3d.hip that moves a layer to another kernel shows up as a diff of this file."""
 import ctypes
 import json

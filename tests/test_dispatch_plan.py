@@ -1,7 +1,7 @@
 """The dispatch is pinned: gz_conv2d_plan / gz_conv3d_plan -- the library's own description of the
 kernel, tile, operand loaders and slab count a launch takes, pure host logic -- must reproduce
 tests/golden/dispatch_plan.json for every convolution layer of the five BASELINE configurations.  A threshold edit in
-csrc/gz_conv.hip, csrc/gz_conv_direct.hip or csrc/gz_conv3d.hip that silently moves a layer onto a slower kernel (parity
+csrc/gz_conv2d_choose.h, csrc/gz_conv_direct.hip or csrc/gz_conv3d.hip that silently moves a layer onto a slower kernel (parity
 stays green) fails here; a deliberate change regenerates the table (python tests/golden/make_dispatch_golden.py) and shows up as its diff."""
 import json
 import os

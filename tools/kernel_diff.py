@@ -1,7 +1,9 @@
 """Are the GPU kernels of two builds the same?  Per kernel: `same`, or the first line that differs.
     python tools/kernel_diff.py OLD NEW [substring ...]
-OLD / NEW are two files of the same kind: device assembly (hipcc --cuda-device-only -S) or HIP objects (.o; their gfx950
-code object is taken out as tools/kernel_regs.py does and disassembled).  Compared per function: the instruction
+OLD / NEW are files of the same kind: device assembly (hipcc --cuda-device-only -S) or HIP objects (.o; their gfx950
+code object is taken out as tools/kernel_regs.py does and disassembled).  Either side may be several files, comma-separated
+(a unit that was split: gz_conv.o against gz_conv.o,gz_conv_fwd.o,...): its functions are the union over them, and a
+function that two files of one side hold must be identical in both -- reported otherwise.  Compared per function: the instruction
 stream -- comments, addresses and the .ident line dropped, local labels numbered per function in order of appearance so
 that neither function order nor label numbering matters -- and per kernel also its descriptor: the .amdhsa_* block
 (assembly) and the metadata note (register counts, scratch, LDS, kernarg bytes).  A plain text diff: it knows nothing
@@ -29,8 +31,10 @@ def metadata(text, out):
 
 def relabel(lines):
     seen = {}
-    sub = lambda m: seen.setdefault(m.group(0), ".L%d" % len(seen))      # noqa: E731
-    return [re.sub(r"\.L[\w$.]+|<L\d+>", sub, ln) for ln in lines]
+    # (a disassembled object numbers its labels through the whole code object, `<L123>:` where defined and `L123` as a
+    # branch operand: both are one label)
+    sub = lambda m: seen.setdefault(m.group(0).strip("<>"), ".L%d" % len(seen))      # noqa: E731
+    return [re.sub(r"\.L[\w$.]+|<L\d+>|\bL\d+\b", sub, ln) for ln in lines]
 
 
 def from_asm(path):
@@ -72,14 +76,29 @@ def from_obj(path):
             body = funcs.setdefault(m.group(1), [])
         elif ln.startswith("s_code_end"):      # (what follows is padding up to the next function)
             body = None
-        elif body is not None and ln:
+        elif body is not None and ln and ln != "...":      # ("...": zero bytes objdump skips, after a file's last function)
             body.append(ln)
     metadata(run(LLVM + "llvm-readelf", "--notes", d + "/k.co"), desc)
     return {k: relabel(v) for k, v in funcs.items()}, desc
 
 
-def load(path):
-    return from_obj(path) if path.endswith(".o") else from_asm(path)
+def load(paths):
+    """The union over the comma-separated files of one side.  A function that several of them hold (a template two units
+    instantiate) must be the same in each: returns also the names where it is not, with the first difference."""
+    funcs, desc, clash = {}, {}, {}
+    for path in paths.split(","):
+        f, d = from_obj(path) if path.endswith(".o") else from_asm(path)
+        for name in f:
+            if name in funcs:
+                diff = first_diff(desc.get(name, []), d.get(name, []))
+                diff = "descriptor " + diff if diff else first_diff(funcs[name], f[name])
+                if diff:
+                    clash.setdefault(name, "differs between files of %s (%s): %s" % (paths, path, diff))
+        for k, v in f.items():
+            funcs.setdefault(k, v)
+        for k, v in d.items():
+            desc.setdefault(k, v)
+    return funcs, desc, clash
 
 
 def first_diff(a, b):
@@ -91,12 +110,14 @@ def first_diff(a, b):
 
 def main():
     old, new, pats = sys.argv[1], sys.argv[2], sys.argv[3:]
-    (fo, do), (fn, dn) = load(old), load(new)
+    (fo, do, co), (fn, dn, cn) = load(old), load(new)
     bad = n_same = 0
     for name in sorted(set(fo) | set(fn)):
         if pats and not all(p in name for p in pats):
             continue
-        if name not in fo or name not in fn:
+        if name in co or name in cn:
+            verdict = co.get(name) or cn[name]
+        elif name not in fo or name not in fn:
             verdict = "only in " + (old if name in fo else new)
         else:
             d = first_diff(do.get(name, []), dn.get(name, []))

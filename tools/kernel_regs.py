@@ -1,5 +1,6 @@
 """Register / LDS / scratch usage of the kernels in a HIP object (from the code object's metadata notes).
-    python tools/kernel_regs.py lightning_gan_zoo_amd/csrc/gz_conv.o [substring ...]"""
+    python tools/kernel_regs.py lightning_gan_zoo_amd/csrc/gz_conv_fwd.o [substring ...]
+(the conv2d launchers are one object per op: gz_conv_fwd.o, gz_conv_dgrad.o, gz_conv_wgrad.o; gz_conv.o has the plain GEMM)"""
 import re
 import subprocess
 import sys
