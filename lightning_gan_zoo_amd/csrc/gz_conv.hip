@@ -130,7 +130,9 @@ int gz_conv2d_dgrad_stats_rows(int N, int C, int H, int W, int K, int OH, int OW
     ConvShape s{N, C, H, W, K, OH, OW};
     if (!shape_ok(s, KH, KW, S, P) || H % S || W % S) return 0;
     const Facts f{true, true, true, kIdeal.ws_bytes, false, true, true};
-#define CALL(G) (dgrad_direct<G>(s) ? Choice{KIgemm, LGeneric, T64x64, 2} : choose_dgrad<G>(s, f))
+    // the choice gz_conv2d_dgrad_stats_ws launches (f.stats: no direct kernel), also for the <= 4-channel shapes of the
+    // direct kernel: their unsplit igemm launch writes tiles_m * WM rows per phase, not one per 32 pixels
+#define CALL(G) choose_dgrad<G>(s, f)
     const Choice sp = [&]() -> Choice { GZ_GEOM_DISPATCH_OR(CALL, (Choice{KIgemm, LGeneric, T64x64, 2})) }();
 #undef CALL
     if (is_tile2(sp.tile) && !(KH == 4 && KW == 4 && S == 2 && P == 1)) return 0;      // gather-loader launches: not fused

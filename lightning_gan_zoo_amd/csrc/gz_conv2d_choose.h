@@ -636,7 +636,11 @@ inline Choice choose_dgrad(const ConvShape& s, const Facts& f) {
         return c;
     }
     if (dgrad_tap_major(s.K, G::kh, G::kw, G::s)) c.loader = LTap;
-    else if (is_k4s2p1<G>() && !knobs().no_row4 && (s.W / 2) % 4 == 0 && f.in16) c.loader = LRow4;    // (GZ_NO_ROW4: per element)
+    // Row4 (GZ_NO_ROW4: per element): the shifted fragment reads stay inside the tile's LDS row only when every tile starts
+    // a row of the per-phase grid (BM % AW == 0, as 256 % OW == 0 for ConvDgA2); 12-, 24- or 48-pixel rows take the
+    // per-element loader
+    else if (is_k4s2p1<G>() && !knobs().no_row4 && (s.W / 2) % 4 == 0 && (c.tile == T64x64 ? 64 : 128) % (s.W / 2) == 0 && f.in16)
+        c.loader = LRow4;
     return c;
 }
 

@@ -76,21 +76,24 @@ def out_side(H, k, s, p):
     return (H + 2 * p - k) // s + 1
 
 
-def conv2d_plan(op, N, C, H, K, k, s, p):
+def conv2d_plan(op, *shape):
+    """``shape``: N C H K k s p (a ConvCase: the square map H x H) or N C H W K k s p (a RectCase)."""
     from lightning_gan_zoo_amd._lib import lib
     buf = ctypes.create_string_buffer(512)
-    OH = out_side(H, k, s, p)
-    rc = lib.gz_conv2d_plan(OPS.index(op), N, C, H, H, K, OH, OH, k, k, s, p, buf, 512)
-    assert rc >= 0, (op, N, C, H, K, k, s, p, rc)
+    N, C, H, W, K, k, s, p = shape if len(shape) == 8 else shape[:3] + (shape[2],) + shape[3:]
+    rc = lib.gz_conv2d_plan(OPS.index(op), N, C, H, W, K, out_side(H, k, s, p), out_side(W, k, s, p), k, k, s, p, buf, 512)
+    assert rc >= 0, (op, shape, rc)
     return buf.value.decode()
 
 
-def conv3d_plan(op, N, C, D, K):
-    """The Conv3d view (make_dispatch_golden.py): image side [N, C, D^3], feature side [N, K, (D/2)^3], k3 s2 p1."""
+def conv3d_plan(op, *shape):
+    """The Conv3d view (make_dispatch_golden.py): image side [N, C, D, H, W], feature side [N, K, D/2, H/2, W/2], k3 s2
+    p1.  ``shape``: N C D K (a Conv3Case: the cube D^3) or N C D H W K (a Box3Case)."""
     from lightning_gan_zoo_amd._lib import lib
     buf = ctypes.create_string_buffer(512)
-    rc = lib.gz_conv3d_plan(OPS.index(op), N, C, D, D, D, K, D // 2, D // 2, D // 2, 3, 2, 1, buf, 512)
-    assert rc >= 0, (op, N, C, D, K, rc)
+    N, C, D, H, W, K = shape if len(shape) == 6 else shape[:3] + (shape[2], shape[2]) + shape[3:]
+    rc = lib.gz_conv3d_plan(OPS.index(op), N, C, D, H, W, K, D // 2, H // 2, W // 2, 3, 2, 1, buf, 512)
+    assert rc >= 0, (op, shape, rc)
     return buf.value.decode()
 
 
@@ -182,28 +185,176 @@ def enumerate_plans(max_macs=1.5e10):
     return best
 
 
+# Rectangular maps (H != W) and box volumes.  The chooser selects most fast loaders by OW alone, and a square power-of-two
+# map has 16 .. 4096 pixels -- always a divisor or a multiple of a 128- / 256- / 512-pixel tile -- so only a rectangle puts
+# an image boundary inside a tile at a position that is no tile boundary ("mid-tile" below).
+RECT_SIDES = [4, 6, 8, 10, 12, 16, 24, 32, 48, 64, 96]
+# (shorter than ENUM_*: with 110 (H, W) pairs the scan is 5 s; the full ENUM_* lists with the odd channel counts of
+# _CONV_TABLE -- 40 s -- reach the same 170 keys, 163 of them mid-tile)
+RECT_NS = [1, 2, 3, 16, 50, 128, 512]
+RECT_CS = [1, 2, 3, 4, 6, 16, 64, 72, 132, 384, 512, 1024]
+RECT_KS = [3, 16, 32, 40, 64, 65, 128, 132, 256, 1024]
+
+
+def tile_pixels(form, op):
+    """Pixels along the tile's row dimension: the first number of igemm<AxB> / igemm2<AxB> for F and Dg.  The weight
+    gradient's tile has no pixel dimension (pixels are its reduction) and a direct kernel has no tile: 256 for both, the
+    workgroup size and the smallest igemm2 tile."""
+    m = re.search(r"igemm2?<(\d+)x", form)
+    return int(m.group(1)) if m and op != "Wg" else 256
+
+
+# the loader families as the plan text names them, most specific first (loader_family() takes the first that matches)
+LOADER_FAMILIES = ["direct", "ConvFwdA2", "ConvDg5A2", "ConvDgA2", "ConvDgTapA2", "ConvTapA2", "WgImgB2", "WgImgBG",
+                   "igemm2r", "Row4", "K4V", "ALoaderTap", "WgALoaderRow", "WgALoader", "ConvFwdALoader", "ConvDgALoader"]
+
+
+def loader_family(form):
+    return next(f for f in LOADER_FAMILIES if f in form)
+
+
+def orientation(shape):
+    """Of a RectCase (or its tuple): "tall" (H > W) or "wide"."""
+    return "tall" if shape[2] > shape[3] else "wide"
+
+
+def mid_tile(N, pixels, tile):
+    """More than one image, and the feature map (per-phase grid of a stride-2 input gradient) neither divides the tile nor
+    is a multiple of it: some tile holds an image boundary that is no tile boundary."""
+    return N > 1 and pixels % tile != 0 and tile % pixels != 0
+
+
+@functools.lru_cache(maxsize=2)
+def _rect_scan(max_macs):
+    """{(plan form, split): {(orientation, mid-tile): (multiply-adds, shape, direction)}}: the cheapest shape per key,
+    orientation ("tall": H > W, "wide": H < W) and whether the shape is mid-tile."""
+    import itertools
+    from lightning_gan_zoo_amd._lib import lib
+    buf = ctypes.create_string_buffer(512)
+    keys, best = {}, {}
+    pairs = [(H, W) for H in RECT_SIDES for W in RECT_SIDES if H != W]
+    for (k, s, p), (H, W) in itertools.product(ENUM_GEOMS, pairs):
+        OH, OW = out_side(H, k, s, p), out_side(W, k, s, p)
+        pixels = (H // s) * (W // s)             # = OH * OW on these even sides: the input gradient's per-phase grid
+        orient = "tall" if H > W else "wide"
+        for N, C, K in itertools.product(RECT_NS, RECT_CS, RECT_KS):
+            macs = N * OH * OW * K * C * k * k
+            if macs > max_macs or N * C * H * W > 1.4e8 or N * K * OH * OW > 1.4e8:
+                continue
+            for i, op in enumerate(OPS):
+                rc = lib.gz_conv2d_plan(i, N, C, H, W, K, OH, OW, k, k, s, p, buf, 512)
+                assert rc >= 0, (op, N, C, H, W, K, k, s, p, rc)
+                text = buf.value
+                key = keys.get(text)
+                if key is None:
+                    t = text.decode()
+                    key = keys[text] = (plan_form(t), split_count(t) > 1)
+                slot = best.setdefault(key, {})
+                which = (orient, mid_tile(N, pixels, tile_pixels(key[0], op)))
+                if which not in slot or macs < slot[which][0]:
+                    slot[which] = (macs, (N, C, H, W, K, k, s, p), op)
+    return best
+
+
+def _cheapest(entries):
+    entries = [e for e in entries if e is not None]
+    return min(entries, key=lambda e: (e[0], e[1])) if entries else None
+
+
+def enumerate_rect_plans(max_macs=1.5e10, orientation=None):
+    """{(plan form, split): (cheapest, mid)} over the (H, W) pairs of RECT_SIDES with H != W, both orientations (or the
+    one asked for), N, C, K of the RECT_* lists, the four layer geometries and the three directions (host only).
+    ``cheapest``: (multiply-adds, shape, direction) of the cheapest rectangle of the key; ``mid``: the same for the
+    cheapest one that is mid_tile(), None where the key has none.  tools/find_exact_cases.py --rect prints the rows."""
+    out = {}
+    for key, slot in _rect_scan(max_macs).items():
+        sides = ("tall", "wide") if orientation is None else (orientation,)
+        cheapest = _cheapest([slot.get((o, m)) for o in sides for m in (False, True)])
+        if cheapest is not None:
+            out[key] = (cheapest, _cheapest([slot.get((o, True)) for o in sides]))
+    return out
+
+
+BOX_SIDES = [4, 6, 8, 10, 12, 16, 24, 32]
+BOX_NS = [1, 2, 5, 16, 24, 64]
+BOX_CS = [1, 4, 16, 64, 72, 128, 130]
+BOX_KS = [8, 20, 64, 72, 128, 512]
+
+
+@functools.lru_cache(maxsize=2)
+def _box_scan(max_macs):
+    """{plan form: {(pairwise different sides, mid-tile): (multiply-adds, shape, direction)}} over the boxes that are no
+    cubes."""
+    import itertools
+    best = {}
+    boxes = [b for b in itertools.product(BOX_SIDES, repeat=3) if len(set(b)) > 1]
+    for (D, H, W), N, C, K in itertools.product(boxes, BOX_NS, BOX_CS, BOX_KS):
+        pixels = (D // 2) * (H // 2) * (W // 2)
+        macs = N * pixels * C * K * 27
+        if macs > max_macs or N * C * D * H * W > 1.4e8:
+            continue
+        for op in OPS:
+            form = plan_form(conv3d_plan(op, N, C, D, H, W, K))
+            which = (len({D, H, W}) == 3, mid_tile(N, pixels, tile_pixels(form, op)))
+            slot = best.setdefault(form, {})
+            if which not in slot or macs < slot[which][0]:
+                slot[which] = (macs, (N, C, D, H, W, K), op)
+    return best
+
+
+def enumerate_box_plans(max_macs=1.5e10):
+    """{plan form: (cheapest, mid)} of conv3d over the boxes of BOX_SIDES^3 that are no cubes, like enumerate_rect_plans
+    (the 3-D table pins the form alone).  Shapes with D, H, W pairwise different are preferred where the form has one."""
+    out = {}
+    for form, slot in _box_scan(max_macs).items():
+        diff = any(k[0] for k in slot)
+        out[form] = (_cheapest([slot.get((d, m)) for d in ((True,) if diff else (False,)) for m in (False, True)]),
+                     _cheapest([slot.get((d, True)) for d in ((True,) if diff else (False,))]))
+    return out
+
+
 # A conv2d case: x [N, C, H, H], w [K, C, k, k], feature side [N, K, OH, OH].
 ConvCase = namedtuple("ConvCase", "N C H K k s p")
+# The same on a rectangular map: x [N, C, H, W], feature side [N, K, OH, OW].  Every helper below takes either.
+RectCase = namedtuple("RectCase", "N C H W K k s p")
+
+
+def conv_case(key):
+    """The case a plain tuple stands for (the lru_cache keys): 7 fields a ConvCase, 8 a RectCase."""
+    return RectCase(*key) if len(key) == 8 else ConvCase(*key)
+
+
+def map_sides(c):
+    """(H, W) of the image side and (OH, OW) of the feature side."""
+    H, W = c.H, getattr(c, "W", c.H)
+    return (H, W), (out_side(H, c.k, c.s, c.p), out_side(W, c.k, c.s, c.p))
 
 
 def case_id(c):
+    if len(c) == 8:
+        return "N%d_C%d_H%dxW%d_K%d_k%ds%dp%d" % tuple(c)
     return "N%d_C%d_H%d_K%d_k%ds%dp%d" % tuple(c[:7])
 
 
+def case_macs(c):
+    _, (OH, OW) = map_sides(c)
+    return c.N * OH * OW * c.K * c.C * c.k * c.k
+
+
 def conv_terms(c, op):
-    OH = out_side(c.H, c.k, c.s, c.p)
+    _, (OH, OW) = map_sides(c)
     if op == "F":
         return c.C * c.k * c.k
     if op == "Dg":
         return c.K * ((c.k + c.s - 1) // c.s) ** 2
-    return c.N * OH * OH
+    return c.N * OH * OW
 
 
 def conv_operands(c, op):
     """(a, b) of direction ``op``: F (x wide, w small), Dg (gy wide, w small), Wg (x wide, gy small)."""
-    OH = out_side(c.H, c.k, c.s, c.p)
-    xs, ws, gs = (c.N, c.C, c.H, c.H), (c.K, c.C, c.k, c.k), (c.N, c.K, OH, OH)
-    seed = 1000 + 7 * OPS.index(op) + (c.N * 31 + c.C * 17 + c.H * 13 + c.K * 11 + c.k) % 997
+    (H, W), (OH, OW) = map_sides(c)
+    xs, ws, gs = (c.N, c.C, H, W), (c.K, c.C, c.k, c.k), (c.N, c.K, OH, OW)
+    seed = 1000 + 7 * OPS.index(op) + (c.N * 31 + c.C * 17 + c.H * 13 + c.K * 11 + c.k + (W * 19 if len(c) == 8 else 0)) % 997
     shapes = {"F": (xs, ws), "Dg": (gs, ws), "Wg": (xs, gs)}[op]
     return pair(shapes[0], shapes[1], conv_terms(c, op), seed)
 
@@ -213,8 +364,9 @@ def conv_apply(c, op, a, b, bias=None):
     if op == "F":
         return TF.conv2d(a, b, bias, c.s, c.p)
     if op == "Dg":
-        OH = out_side(c.H, c.k, c.s, c.p)
-        return TF.conv_transpose2d(a, b, bias, c.s, c.p, output_padding=c.H - ((OH - 1) * c.s - 2 * c.p + c.k))
+        sides, outs = map_sides(c)
+        return TF.conv_transpose2d(a, b, bias, c.s, c.p,
+                                   output_padding=tuple(h - ((o - 1) * c.s - 2 * c.p + c.k) for h, o in zip(sides, outs)))
     return torch.nn.grad.conv2d_weight(a, (c.K, c.C, c.k, c.k), b, stride=c.s, padding=c.p)
 
 
@@ -225,7 +377,7 @@ def set_threads():
 @functools.lru_cache(maxsize=4)
 def conv_reference(c_key, op):
     """(a, b, ref64) with the precondition asserted; computed once per (case, direction) and shared."""
-    c = ConvCase(*c_key)
+    c = conv_case(c_key)
     set_threads()
     a, b = conv_operands(c, op)
     assert_exact_precondition(conv_apply(c, op, a.double().abs(), b.double().abs()), "%s %s" % (case_id(c), op))
@@ -428,6 +580,9 @@ _CONV_TABLE = [
     # launch_igemm2 with more than 16 slabs (22: the eight-wavefront finish pass), one wave group, equal phases -- the one
     # path of launch_paths() that only the wave_groups=2 and the per-phase launches above reached
     ((33, 512, 8, 256, 5, 2, 2), 'F', 'F igemm2<256x64> ConvTapA2(gather, LDS-DMA 4B) slabs= bn_stats_rows=', True),
+    # a square with 12-pixel rows per phase (H = 24): no tile of 64 or 128 pixels holds whole rows, so the k4 s2 p1 input
+    # gradient stays off ConvDgALoaderRow4 (found by the rectangular table below)
+    ((3, 64, 24, 3, 4, 2, 1), 'Dg', 'Dg igemm<64x64> ConvDgALoader splits= bn_stats_rows=', False),
 ]
 CONV_ROWS = [(ConvCase(*sh), op, form, split) for sh, op, form, split in _CONV_TABLE]
 
@@ -486,23 +641,43 @@ _CONV3_TABLE = [
 CONV3_ROWS = [(Conv3Case(*c), op, form) for c, op, form in _CONV3_TABLE]
 
 
+# The same on a box: image side [N, C, D, H, W] (even sides), feature side [N, K, D/2, H/2, W/2].
+Box3Case = namedtuple("Box3Case", "N C D H W K")
+
+
+def conv3_case(key):
+    return Box3Case(*key) if len(key) == 6 else Conv3Case(*key)
+
+
+def box_sides(c):
+    return (c.D, c.H, c.W) if len(c) == 6 else (c.D, c.D, c.D)
+
+
 def row3_id(row):
+    if len(row[0]) == 6:
+        return "%s-N%d_C%d_D%dxH%dxW%d_K%d" % ((row[1],) + tuple(row[0]))
     return "%s-N%d_C%d_D%d_K%d" % ((row[1],) + tuple(row[0]))
 
 
+def box_pixels(c):
+    D, H, W = box_sides(c)
+    return (D // 2) * (H // 2) * (W // 2)
+
+
 def row3_macs(c):
-    return c.N * (c.D // 2) ** 3 * c.C * c.K * 27
+    return c.N * box_pixels(c) * c.C * c.K * 27
 
 
 def conv3_terms(c, op):
-    return {"F": c.C * 27, "Dg": c.K * 8, "Wg": c.N * (c.D // 2) ** 3}[op]
+    return {"F": c.C * 27, "Dg": c.K * 8, "Wg": c.N * box_pixels(c)}[op]
 
 
 def conv3_operands(c, op):
-    OD = c.D // 2
-    xs, ws, gs = (c.N, c.C, c.D, c.D, c.D), (c.K, c.C, 3, 3, 3), (c.N, c.K, OD, OD, OD)
+    D, H, W = box_sides(c)
+    xs, ws, gs = (c.N, c.C, D, H, W), (c.K, c.C, 3, 3, 3), (c.N, c.K, D // 2, H // 2, W // 2)
     shapes = {"F": (xs, ws), "Dg": (gs, ws), "Wg": (xs, gs)}[op]
-    return pair(shapes[0], shapes[1], conv3_terms(c, op), 3000 + OPS.index(op) + c.N + c.C + c.K)
+    seed = 3000 + OPS.index(op) + c.N + c.C + c.K + (3 * D + 5 * H + 7 * W if len(c) == 6 else 0)
+    return pair(shapes[0], shapes[1], conv3_terms(c, op), seed)
 
 
 def conv3_apply(c, op, a, b, bias=None):
@@ -515,11 +690,236 @@ def conv3_apply(c, op, a, b, bias=None):
 
 @functools.lru_cache(maxsize=4)
 def conv3_reference(key, op):
-    c = Conv3Case(*key)
+    c = conv3_case(key)
     set_threads()
     a, b = conv3_operands(c, op)
     assert_exact_precondition(conv3_apply(c, op, a.double().abs(), b.double().abs()), "3d %s %s" % (key, op))
     return a, b, conv3_apply(c, op, a.double(), b.double())
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# rectangular maps and box volumes: one row per (form, split) key that enumerate_rect_plans() reaches -- all 162 keys of
+# _CONV_TABLE and 8 that no square of it reaches -- as printed by tools/find_exact_cases.py --rect.  A row is the cheapest
+# mid-tile shape of its key (N > 1, the feature map neither a divisor nor a multiple of the tile's pixel count), or the
+# cheapest rectangle where the key has none ("no mid-tile").  RECT_MID_KEYS of the RECT_KEYS keys have a mid-tile row.
+# The orientation alternates down the table; every loader family has a tall (H > W) and a wide row per direction, for
+# which ConvFwdALoaderRow4 needs a second row (its tall maps, 16- or 32-pixel rows and >= 24 of them, are whole tiles).
+# "sq": a square row of the same key is cheaper than this rectangle, which is over 3e9 multiply-adds.
+# ---------------------------------------------------------------------------------------------------------------------
+RECT_KEYS, RECT_MID_KEYS = 170, 163
+_DG5A2 = ('Dg igemm2<256x(4 phases x 32)> ConvDg5A2(row-shared, LDS-DMA 16B, 12 k-steps) slabs= (no bias / activation, '
+          'aligned tensors; else the gather loader)')
+_RECT_TABLE = [
+    ((128, 1, 6, 96, 16, 3, 1, 1), 'Dg', 'Dg direct conv3x3_smallch<mfma16x16x4>', False),
+    ((2, 1, 6, 8, 3, 4, 2, 1), 'Dg', 'Dg direct dgrad_smallc4_k4s2p1<C=1,KS=1>', False),
+    ((2, 1, 10, 8, 16, 4, 2, 1), 'Dg', 'Dg direct dgrad_smallc4_k4s2p1<C=1,KS=4>', False),
+    ((2, 1, 6, 8, 32, 4, 2, 1), 'Dg', 'Dg direct dgrad_smallc4_k4s2p1<C=1,KS=8>', False),
+    ((2, 2, 10, 8, 3, 4, 2, 1), 'Dg', 'Dg direct dgrad_smallc4_k4s2p1<C=2,KS=1>', False),
+    ((2, 2, 6, 8, 16, 4, 2, 1), 'Dg', 'Dg direct dgrad_smallc4_k4s2p1<C=2,KS=4>', False),
+    ((2, 2, 10, 8, 32, 4, 2, 1), 'Dg', 'Dg direct dgrad_smallc4_k4s2p1<C=2,KS=8>', False),
+    ((2, 3, 6, 8, 3, 4, 2, 1), 'Dg', 'Dg direct dgrad_smallc4_k4s2p1<C=3,KS=1>', False),
+    ((2, 3, 10, 8, 16, 4, 2, 1), 'Dg', 'Dg direct dgrad_smallc4_k4s2p1<C=3,KS=4>', False),
+    ((2, 3, 6, 8, 32, 4, 2, 1), 'Dg', 'Dg direct dgrad_smallc4_k4s2p1<C=3,KS=8>', False),
+    ((2, 4, 10, 8, 3, 4, 2, 1), 'Dg', 'Dg direct dgrad_smallc4_k4s2p1<C=4,KS=1>', False),
+    ((2, 4, 6, 8, 16, 4, 2, 1), 'Dg', 'Dg direct dgrad_smallc4_k4s2p1<C=4,KS=4>', False),
+    ((2, 4, 10, 8, 32, 4, 2, 1), 'Dg', 'Dg direct dgrad_smallc4_k4s2p1<C=4,KS=8>', False),
+    ((512, 1, 96, 64, 16, 5, 2, 2), 'Dg', 'Dg direct dgrad_smallc4_k5s2p2<C=1,KS=1>', False),        # no mid-tile
+    ((2, 1, 10, 8, 16, 5, 2, 2), 'Dg', 'Dg direct dgrad_smallc4_k5s2p2<C=1,KS=4>', False),
+    ((2, 1, 6, 8, 32, 5, 2, 2), 'Dg', 'Dg direct dgrad_smallc4_k5s2p2<C=1,KS=8>', False),
+    ((512, 2, 96, 64, 16, 5, 2, 2), 'Dg', 'Dg direct dgrad_smallc4_k5s2p2<C=2,KS=1>', False),        # no mid-tile
+    ((2, 2, 6, 8, 16, 5, 2, 2), 'Dg', 'Dg direct dgrad_smallc4_k5s2p2<C=2,KS=4>', False),
+    ((2, 2, 10, 8, 32, 5, 2, 2), 'Dg', 'Dg direct dgrad_smallc4_k5s2p2<C=2,KS=8>', False),
+    ((512, 3, 96, 64, 16, 5, 2, 2), 'Dg', 'Dg direct dgrad_smallc4_k5s2p2<C=3,KS=1>', False),        # no mid-tile
+    ((2, 3, 10, 8, 16, 5, 2, 2), 'Dg', 'Dg direct dgrad_smallc4_k5s2p2<C=3,KS=4>', False),
+    ((2, 3, 6, 8, 32, 5, 2, 2), 'Dg', 'Dg direct dgrad_smallc4_k5s2p2<C=3,KS=8>', False),
+    ((512, 4, 96, 64, 16, 5, 2, 2), 'Dg', 'Dg direct dgrad_smallc4_k5s2p2<C=4,KS=1>', False),        # no mid-tile
+    ((2, 4, 6, 8, 16, 5, 2, 2), 'Dg', 'Dg direct dgrad_smallc4_k5s2p2<C=4,KS=4>', False),
+    ((2, 4, 10, 8, 32, 5, 2, 2), 'Dg', 'Dg direct dgrad_smallc4_k5s2p2<C=4,KS=8>', False),
+    ((2, 1, 4, 6, 3, 4, 2, 1), 'Dg', 'Dg direct dgrad_smallc_k4s2p1<C=1>', False),
+    ((2, 2, 6, 4, 3, 4, 2, 1), 'Dg', 'Dg direct dgrad_smallc_k4s2p1<C=2>', False),
+    ((2, 3, 4, 6, 3, 4, 2, 1), 'Dg', 'Dg direct dgrad_smallc_k4s2p1<C=3>', False),
+    ((2, 4, 6, 4, 3, 4, 2, 1), 'Dg', 'Dg direct dgrad_smallc_k4s2p1<C=4>', False),
+    ((50, 384, 12, 64, 128, 5, 2, 2), 'Dg', _DG5A2, False),
+    ((3, 1024, 24, 16, 1024, 5, 2, 2), 'Dg', _DG5A2, True),
+    ((50, 132, 10, 64, 64, 4, 2, 1), 'Dg', 'Dg igemm2<256x128> ConvDgA2(row-shared, LDS-DMA 16B) splits= bn_stats_rows=', False),
+    ((50, 132, 24, 16, 256, 4, 2, 1), 'Dg', 'Dg igemm2<256x128> ConvDgA2(row-shared, LDS-DMA 16B) splits= bn_stats_rows=', True),
+    ((50, 132, 10, 64, 128, 4, 2, 1), 'Dg', 'Dg igemm2<256x128> ConvDgA2(row-shared, LDS-DMA 16B) splits= bn_stats_rows= wave_groups=2', False),
+    ((50, 132, 10, 32, 256, 4, 2, 1), 'Dg', 'Dg igemm2<256x128> ConvDgA2(row-shared, LDS-DMA 16B) splits= bn_stats_rows= wave_groups=2', True),
+    ((50, 132, 6, 96, 128, 1, 1, 0), 'Dg', 'Dg igemm2<256x128> ConvDgTapA2(gather, LDS-DMA 4B) splits= bn_stats_rows=', False),
+    ((50, 132, 32, 24, 132, 5, 2, 2), 'Dg', 'Dg igemm2<256x128> ConvDgTapA2(gather, LDS-DMA 4B) splits= bn_stats_rows=', True),
+    ((50, 132, 6, 96, 64, 3, 1, 1), 'Dg', 'Dg igemm2<256x128> ConvDgTapA2(gather, LDS-DMA 4B) splits= bn_stats_rows= wave_groups=2', False),
+    ((50, 132, 24, 12, 256, 3, 1, 1), 'Dg', 'Dg igemm2<256x128> ConvDgTapA2(gather, LDS-DMA 4B) splits= bn_stats_rows= wave_groups=2', True),
+    ((50, 384, 10, 64, 64, 4, 2, 1), 'Dg', 'Dg igemm2<256x256> ConvDgA2(row-shared, LDS-DMA 16B) splits= bn_stats_rows=', False),
+    ((50, 1024, 10, 8, 64, 4, 2, 1), 'Dg', 'Dg igemm2<256x64> ConvDgA2(row-shared, LDS-DMA 16B) splits= bn_stats_rows=', False),
+    ((128, 384, 6, 8, 256, 4, 2, 1), 'Dg', 'Dg igemm2<256x64> ConvDgA2(row-shared, LDS-DMA 16B) splits= bn_stats_rows=', True),
+    ((50, 1024, 10, 8, 128, 4, 2, 1), 'Dg', 'Dg igemm2<256x64> ConvDgA2(row-shared, LDS-DMA 16B) splits= bn_stats_rows= wave_groups=2', False),
+    ((3, 1024, 6, 64, 256, 4, 2, 1), 'Dg', 'Dg igemm2<256x64> ConvDgA2(row-shared, LDS-DMA 16B) splits= bn_stats_rows= wave_groups=2', True),
+    ((3, 1024, 96, 24, 40, 5, 2, 2), 'Dg', 'Dg igemm2<256x64> ConvDgTapA2(gather, LDS-DMA 4B) splits= bn_stats_rows=', False),
+    ((2, 384, 4, 6, 1024, 5, 2, 2), 'Dg', 'Dg igemm2<256x64> ConvDgTapA2(gather, LDS-DMA 4B) splits= bn_stats_rows=', True),
+    ((512, 64, 48, 16, 64, 4, 2, 1), 'Dg', 'Dg igemm2<512x64> ConvDgA2(row-shared, LDS-DMA 16B) splits= bn_stats_rows=', False),        # 6.4e9; sq 4.3e9
+    ((2, 132, 4, 6, 3, 1, 1, 0), 'Dg', 'Dg igemm<128x128> ConvDgALoader splits= bn_stats_rows=', False),
+    ((2, 132, 6, 4, 64, 4, 2, 1), 'Dg', 'Dg igemm<128x128> ConvDgALoader splits= bn_stats_rows=', True),
+    ((2, 132, 6, 8, 3, 4, 2, 1), 'Dg', 'Dg igemm<128x128> ConvDgALoaderRow4 splits= bn_stats_rows=', False),
+    ((2, 132, 10, 8, 64, 4, 2, 1), 'Dg', 'Dg igemm<128x128> ConvDgALoaderRow4 splits= bn_stats_rows=', True),
+    ((2, 132, 4, 6, 16, 5, 2, 2), 'Dg', 'Dg igemm<128x128> ConvDgALoaderTap splits= bn_stats_rows=', False),
+    ((2, 132, 6, 4, 32, 5, 2, 2), 'Dg', 'Dg igemm<128x128> ConvDgALoaderTap splits= bn_stats_rows=', True),
+    ((2, 1, 4, 6, 3, 1, 1, 0), 'Dg', 'Dg igemm<128x32> ConvDgALoader splits= bn_stats_rows=', False),
+    ((2, 1, 6, 4, 256, 1, 1, 0), 'Dg', 'Dg igemm<128x32> ConvDgALoader splits= bn_stats_rows=', True),
+    ((2, 6, 6, 8, 3, 4, 2, 1), 'Dg', 'Dg igemm<128x32> ConvDgALoaderRow4 splits= bn_stats_rows=', False),
+    ((2, 6, 10, 8, 64, 4, 2, 1), 'Dg', 'Dg igemm<128x32> ConvDgALoaderRow4 splits= bn_stats_rows=', True),
+    ((2, 1, 4, 6, 16, 5, 2, 2), 'Dg', 'Dg igemm<128x32> ConvDgALoaderTap splits= bn_stats_rows=', False),
+    ((2, 1, 6, 4, 32, 5, 2, 2), 'Dg', 'Dg igemm<128x32> ConvDgALoaderTap splits= bn_stats_rows=', True),
+    ((2, 64, 4, 6, 3, 1, 1, 0), 'Dg', 'Dg igemm<128x64> ConvDgALoader splits= bn_stats_rows=', False),
+    ((2, 64, 6, 4, 64, 4, 2, 1), 'Dg', 'Dg igemm<128x64> ConvDgALoader splits= bn_stats_rows=', True),
+    ((2, 64, 6, 8, 3, 4, 2, 1), 'Dg', 'Dg igemm<128x64> ConvDgALoaderRow4 splits= bn_stats_rows=', False),
+    ((2, 64, 10, 8, 64, 4, 2, 1), 'Dg', 'Dg igemm<128x64> ConvDgALoaderRow4 splits= bn_stats_rows=', True),
+    ((2, 64, 4, 6, 16, 5, 2, 2), 'Dg', 'Dg igemm<128x64> ConvDgALoaderTap splits= bn_stats_rows=', False),
+    ((2, 64, 6, 4, 32, 5, 2, 2), 'Dg', 'Dg igemm<128x64> ConvDgALoaderTap splits= bn_stats_rows=', True),
+    ((3, 64, 4, 6, 3, 1, 1, 0), 'Dg', 'Dg igemm<64x64> ConvDgALoader splits= bn_stats_rows=', False),
+    ((3, 64, 6, 4, 256, 1, 1, 0), 'Dg', 'Dg igemm<64x64> ConvDgALoader splits= bn_stats_rows=', True),
+    ((3, 64, 6, 16, 3, 4, 2, 1), 'Dg', 'Dg igemm<64x64> ConvDgALoaderRow4 splits= bn_stats_rows=', False),
+    ((3, 64, 12, 8, 64, 4, 2, 1), 'Dg', 'Dg igemm<64x64> ConvDgALoaderRow4 splits= bn_stats_rows=', True),
+    ((3, 64, 4, 6, 16, 3, 1, 1), 'Dg', 'Dg igemm<64x64> ConvDgALoaderTap splits= bn_stats_rows=', False),
+    ((3, 64, 6, 4, 32, 3, 1, 1), 'Dg', 'Dg igemm<64x64> ConvDgALoaderTap splits= bn_stats_rows=', True),
+    ((16, 16, 96, 64, 3, 3, 1, 1), 'F', 'F direct conv3x3_fewk<fma>', False),        # no mid-tile
+    ((128, 16, 6, 96, 3, 3, 1, 1), 'F', 'F direct conv3x3_smallch<mfma16x16x4>', False),
+    ((512, 16, 10, 32, 132, 4, 2, 1), 'F', 'F igemm2<256x128> ConvFwdA2(raw rows, LDS-DMA 16B) slabs= bn_stats_rows=', False),
+    ((128, 384, 12, 8, 132, 4, 2, 1), 'F', 'F igemm2<256x128> ConvFwdA2(raw rows, LDS-DMA 16B) slabs= bn_stats_rows=', True),
+    ((50, 64, 10, 64, 1024, 4, 2, 1), 'F', 'F igemm2<256x128> ConvFwdA2(raw rows, LDS-DMA 16B) slabs= bn_stats_rows= wave_groups=2', False),        # 8.4e9; sq 4.4e9
+    ((50, 512, 10, 16, 132, 4, 2, 1), 'F', 'F igemm2<256x128> ConvFwdA2(raw rows, LDS-DMA 16B) slabs= bn_stats_rows= wave_groups=2', True),
+    ((50, 16, 6, 96, 132, 1, 1, 0), 'F', 'F igemm2<256x128> ConvTapA2(gather, LDS-DMA 4B) slabs= bn_stats_rows=', False),
+    ((50, 1024, 12, 6, 132, 3, 1, 1), 'F', 'F igemm2<256x128> ConvTapA2(gather, LDS-DMA 4B) slabs= bn_stats_rows=', True),
+    ((50, 64, 6, 96, 132, 3, 1, 1), 'F', 'F igemm2<256x128> ConvTapA2(gather, LDS-DMA 4B) slabs= bn_stats_rows= wave_groups=2', False),
+    ((2, 1024, 6, 4, 1024, 5, 2, 2), 'F', 'F igemm2<256x128> ConvTapA2(gather, LDS-DMA 4B) slabs= bn_stats_rows= wave_groups=2', True),
+    ((50, 16, 10, 32, 1024, 4, 2, 1), 'F', 'F igemm2<256x64> ConvFwdA2(raw rows, LDS-DMA 16B) slabs= bn_stats_rows=', False),
+    ((3, 132, 48, 32, 1024, 4, 2, 1), 'F', 'F igemm2<256x64> ConvFwdA2(raw rows, LDS-DMA 16B) slabs= bn_stats_rows=', True),
+    ((50, 64, 10, 32, 1024, 4, 2, 1), 'F', 'F igemm2<256x64> ConvFwdA2(raw rows, LDS-DMA 16B) slabs= bn_stats_rows= wave_groups=2', False),
+    ((3, 384, 24, 16, 1024, 4, 2, 1), 'F', 'F igemm2<256x64> ConvFwdA2(raw rows, LDS-DMA 16B) slabs= bn_stats_rows= wave_groups=2', True),
+    ((3, 512, 10, 96, 1024, 1, 1, 0), 'F', 'F igemm2<256x64> ConvTapA2(gather, LDS-DMA 4B) slabs= bn_stats_rows=', False),
+    ((3, 1024, 48, 10, 1024, 1, 1, 0), 'F', 'F igemm2<256x64> ConvTapA2(gather, LDS-DMA 4B) slabs= bn_stats_rows=', True),
+    ((3, 64, 10, 96, 1024, 3, 1, 1), 'F', 'F igemm2<256x64> ConvTapA2(gather, LDS-DMA 4B) slabs= bn_stats_rows= wave_groups=2', False),
+    ((2, 384, 6, 4, 1024, 5, 2, 2), 'F', 'F igemm2<256x64> ConvTapA2(gather, LDS-DMA 4B) slabs= bn_stats_rows= wave_groups=2', True),
+    ((2, 1, 4, 6, 132, 1, 1, 0), 'F', 'F igemm<128x128> ConvFwdALoader slabs= bn_stats_rows=', False),
+    ((2, 384, 6, 4, 132, 1, 1, 0), 'F', 'F igemm<128x128> ConvFwdALoader slabs= bn_stats_rows=', True),
+    ((2, 1, 4, 6, 132, 4, 2, 1), 'F', 'F igemm<128x128> ConvFwdALoaderK4V slabs= bn_stats_rows=', False),
+    ((2, 16, 6, 4, 132, 4, 2, 1), 'F', 'F igemm<128x128> ConvFwdALoaderK4V slabs= bn_stats_rows=', True),
+    ((3, 1, 6, 32, 132, 4, 2, 1), 'F', 'F igemm<128x128> ConvFwdALoaderRow4 slabs= bn_stats_rows=', False),
+    ((3, 16, 6, 32, 132, 4, 2, 1), 'F', 'F igemm<128x128> ConvFwdALoaderRow4 slabs= bn_stats_rows=', True),
+    ((2, 16, 4, 6, 132, 3, 1, 1), 'F', 'F igemm<128x128> ConvFwdALoaderTap slabs= bn_stats_rows=', False),
+    ((2, 16, 6, 4, 132, 5, 2, 2), 'F', 'F igemm<128x128> ConvFwdALoaderTap slabs= bn_stats_rows=', True),
+    ((2, 1, 4, 6, 3, 1, 1, 0), 'F', 'F igemm<128x32> ConvFwdALoader slabs= bn_stats_rows=', False),
+    ((2, 384, 6, 4, 3, 1, 1, 0), 'F', 'F igemm<128x32> ConvFwdALoader slabs= bn_stats_rows=', True),
+    ((2, 1, 4, 6, 3, 4, 2, 1), 'F', 'F igemm<128x32> ConvFwdALoaderK4V slabs= bn_stats_rows=', False),
+    ((2, 16, 6, 4, 3, 4, 2, 1), 'F', 'F igemm<128x32> ConvFwdALoaderK4V slabs= bn_stats_rows=', True),
+    ((2, 1, 6, 32, 3, 4, 2, 1), 'F', 'F igemm<128x32> ConvFwdALoaderRow4 slabs= bn_stats_rows=', False),
+    ((2, 16, 6, 32, 3, 4, 2, 1), 'F', 'F igemm<128x32> ConvFwdALoaderRow4 slabs= bn_stats_rows=', True),
+    ((2, 16, 4, 6, 3, 3, 1, 1), 'F', 'F igemm<128x32> ConvFwdALoaderTap slabs= bn_stats_rows=', False),
+    ((2, 16, 6, 4, 3, 5, 2, 2), 'F', 'F igemm<128x32> ConvFwdALoaderTap slabs= bn_stats_rows=', True),
+    ((2, 1, 4, 6, 40, 1, 1, 0), 'F', 'F igemm<128x64> ConvFwdALoader slabs= bn_stats_rows=', False),
+    ((2, 384, 6, 4, 40, 1, 1, 0), 'F', 'F igemm<128x64> ConvFwdALoader slabs= bn_stats_rows=', True),
+    ((2, 1, 4, 6, 40, 4, 2, 1), 'F', 'F igemm<128x64> ConvFwdALoaderK4V slabs= bn_stats_rows=', False),
+    ((2, 16, 6, 4, 40, 4, 2, 1), 'F', 'F igemm<128x64> ConvFwdALoaderK4V slabs= bn_stats_rows=', True),
+    ((512, 1, 10, 64, 65, 4, 2, 1), 'F', 'F igemm<128x64> ConvFwdALoaderRow4 slabs= bn_stats_rows=', False),
+    ((1, 16, 4, 32, 40, 4, 2, 1), 'F', 'F igemm<128x64> ConvFwdALoaderRow4 slabs= bn_stats_rows=', True),        # no mid-tile
+    ((2, 16, 4, 6, 40, 3, 1, 1), 'F', 'F igemm<128x64> ConvFwdALoaderTap slabs= bn_stats_rows=', False),
+    ((2, 16, 6, 4, 40, 5, 2, 2), 'F', 'F igemm<128x64> ConvFwdALoaderTap slabs= bn_stats_rows=', True),
+    ((3, 1, 4, 6, 40, 1, 1, 0), 'F', 'F igemm<64x64> ConvFwdALoader slabs= bn_stats_rows=', False),
+    ((3, 384, 6, 4, 40, 1, 1, 0), 'F', 'F igemm<64x64> ConvFwdALoader slabs= bn_stats_rows=', True),
+    ((3, 1, 4, 24, 40, 4, 2, 1), 'F', 'F igemm<64x64> ConvFwdALoaderK4V slabs= bn_stats_rows=', False),
+    ((3, 16, 12, 8, 40, 4, 2, 1), 'F', 'F igemm<64x64> ConvFwdALoaderK4V slabs= bn_stats_rows=', True),
+    ((2, 1, 6, 32, 40, 4, 2, 1), 'F', 'F igemm<64x64> ConvFwdALoaderRow4 slabs= bn_stats_rows=', False),
+    ((2, 16, 6, 32, 40, 4, 2, 1), 'F', 'F igemm<64x64> ConvFwdALoaderRow4 slabs= bn_stats_rows=', True),
+    ((3, 16, 4, 6, 40, 3, 1, 1), 'F', 'F igemm<64x64> ConvFwdALoaderTap slabs= bn_stats_rows=', False),
+    ((3, 16, 12, 8, 40, 5, 2, 2), 'F', 'F igemm<64x64> ConvFwdALoaderTap slabs= bn_stats_rows=', True),
+    ((128, 1, 8, 64, 3, 3, 1, 1), 'Wg', 'Wg direct wgrad_k3_fewk<fma> slabs=', True),        # no mid-tile
+    ((50, 1, 48, 32, 16, 4, 2, 1), 'Wg', 'Wg direct wgrad_k4s2p1_fewc<mfma16x16x4,C=1,KT=1> slabs=', True),
+    ((128, 1, 6, 96, 32, 4, 2, 1), 'Wg', 'Wg direct wgrad_k4s2p1_fewc<mfma16x16x4,C=1,KT=2> slabs=', True),
+    ((50, 1, 48, 32, 64, 4, 2, 1), 'Wg', 'Wg direct wgrad_k4s2p1_fewc<mfma16x16x4,C=1,KT=4> slabs=', True),
+    ((128, 2, 6, 96, 16, 4, 2, 1), 'Wg', 'Wg direct wgrad_k4s2p1_fewc<mfma16x16x4,C=2,KT=1> slabs=', True),
+    ((50, 2, 48, 32, 32, 4, 2, 1), 'Wg', 'Wg direct wgrad_k4s2p1_fewc<mfma16x16x4,C=2,KT=2> slabs=', True),
+    ((128, 2, 6, 96, 64, 4, 2, 1), 'Wg', 'Wg direct wgrad_k4s2p1_fewc<mfma16x16x4,C=2,KT=4> slabs=', True),
+    ((50, 3, 48, 32, 16, 4, 2, 1), 'Wg', 'Wg direct wgrad_k4s2p1_fewc<mfma16x16x4,C=3,KT=1> slabs=', True),
+    ((128, 3, 6, 96, 32, 4, 2, 1), 'Wg', 'Wg direct wgrad_k4s2p1_fewc<mfma16x16x4,C=3,KT=2> slabs=', True),
+    ((50, 3, 48, 32, 64, 4, 2, 1), 'Wg', 'Wg direct wgrad_k4s2p1_fewc<mfma16x16x4,C=3,KT=4> slabs=', True),
+    ((128, 4, 6, 96, 16, 4, 2, 1), 'Wg', 'Wg direct wgrad_k4s2p1_fewc<mfma16x16x4,C=4,KT=1> slabs=', True),
+    ((50, 4, 48, 32, 32, 4, 2, 1), 'Wg', 'Wg direct wgrad_k4s2p1_fewc<mfma16x16x4,C=4,KT=2> slabs=', True),
+    ((128, 4, 6, 96, 64, 4, 2, 1), 'Wg', 'Wg direct wgrad_k4s2p1_fewc<mfma16x16x4,C=4,KT=4> slabs=', True),
+    ((128, 1, 6, 96, 3, 3, 1, 1), 'Wg', 'Wg direct wgrad_smallch_k3<mfma16x16x4> slabs=', True),
+    # igemm2r on 2-D maps: feature rows of 2 pixels (W = 4, OH a multiple of 8), so tall maps only
+    ((128, 384, 96, 4, 128, 4, 2, 1), 'Wg', 'Wg igemm2r<128x256> WgALoaderRow+WgBLoaderRow(register-staged) slabs=', True),
+    ((2, 512, 48, 4, 1024, 4, 2, 1), 'Wg', 'Wg igemm2r<256x128> WgALoaderRow+WgBLoaderRow(register-staged) slabs=', False),
+    ((128, 384, 48, 4, 256, 4, 2, 1), 'Wg', 'Wg igemm2r<256x128> WgALoaderRow+WgBLoaderRow(register-staged) slabs=', True),
+    ((16, 384, 48, 32, 128, 4, 2, 1), 'Wg', 'Wg igemm2w<128x256> WgImgB2<CW=16>(both operands LDS-DMA) slabs=', True),        # 4.8e9; sq 4.3e9
+    ((128, 384, 24, 8, 128, 4, 2, 1), 'Wg', 'Wg igemm2w<128x256> WgImgB2<CW=4>(both operands LDS-DMA) slabs=', True),        # 4.8e9; sq 2.7e9
+    ((16, 384, 96, 16, 128, 4, 2, 1), 'Wg', 'Wg igemm2w<128x256> WgImgB2<CW=8>(both operands LDS-DMA) slabs=', True),        # 4.8e9; sq 2.8e9
+    ((50, 64, 10, 96, 128, 3, 1, 1), 'Wg', 'Wg igemm2w<128x256> WgImgBG<CW=16>(both operands LDS-DMA) slabs=', True),
+    ((512, 64, 24, 4, 128, 3, 1, 1), 'Wg', 'Wg igemm2w<128x256> WgImgBG<CW=4>(both operands LDS-DMA) slabs=', True),        # 3.6e9; sq 2.4e9
+    ((512, 64, 12, 16, 128, 5, 2, 2), 'Wg', 'Wg igemm2w<128x256> WgImgBG<CW=8>(both operands LDS-DMA) slabs=', True),        # 5.0e9; sq 2.4e9
+    ((2, 512, 6, 32, 1024, 4, 2, 1), 'Wg', 'Wg igemm2w<256x128> WgImgB2<CW=16>(both operands LDS-DMA) slabs=', False),
+    ((16, 512, 6, 96, 256, 4, 2, 1), 'Wg', 'Wg igemm2w<256x128> WgImgB2<CW=16>(both operands LDS-DMA) slabs=', True),        # 4.8e9; sq 4.3e9
+    ((2, 512, 24, 8, 1024, 4, 2, 1), 'Wg', 'Wg igemm2w<256x128> WgImgB2<CW=4>(both operands LDS-DMA) slabs=', False),
+    ((16, 384, 96, 8, 256, 4, 2, 1), 'Wg', 'Wg igemm2w<256x128> WgImgB2<CW=4>(both operands LDS-DMA) slabs=', True),        # 4.8e9; sq 4.3e9
+    ((2, 512, 24, 16, 1024, 4, 2, 1), 'Wg', 'Wg igemm2w<256x128> WgImgB2<CW=8>(both operands LDS-DMA) slabs=', False),
+    ((50, 512, 12, 16, 256, 4, 2, 1), 'Wg', 'Wg igemm2w<256x128> WgImgB2<CW=8>(both operands LDS-DMA) slabs=', True),        # 5.0e9; sq 4.3e9
+    ((2, 384, 6, 32, 1024, 5, 2, 2), 'Wg', 'Wg igemm2w<256x128> WgImgBG<CW=16>(both operands LDS-DMA) slabs=', False),
+    ((128, 16, 6, 96, 256, 3, 1, 1), 'Wg', 'Wg igemm2w<256x128> WgImgBG<CW=16>(both operands LDS-DMA) slabs=', True),
+    ((2, 1024, 12, 4, 1024, 3, 1, 1), 'Wg', 'Wg igemm2w<256x128> WgImgBG<CW=4>(both operands LDS-DMA) slabs=', False),
+    ((50, 16, 96, 4, 1024, 3, 1, 1), 'Wg', 'Wg igemm2w<256x128> WgImgBG<CW=4>(both operands LDS-DMA) slabs=', True),
+    ((2, 1024, 10, 8, 1024, 3, 1, 1), 'Wg', 'Wg igemm2w<256x128> WgImgBG<CW=8>(both operands LDS-DMA) slabs=', False),
+    ((512, 16, 6, 8, 1024, 3, 1, 1), 'Wg', 'Wg igemm2w<256x128> WgImgBG<CW=8>(both operands LDS-DMA) slabs=', True),        # 3.6e9; sq 2.4e9
+    ((128, 72, 12, 6, 65, 1, 1, 0), 'Wg', 'Wg igemm<128x128> WgALoader+WgBLoader slabs=', True),
+    ((16, 72, 6, 96, 65, 1, 1, 0), 'Wg', 'Wg igemm<128x128> WgALoaderRow+WgBLoaderRow slabs=', True),
+    ((2, 1, 6, 4, 3, 1, 1, 0), 'Wg', 'Wg igemm<128x32> WgALoader+WgBLoader slabs=', False),
+    ((3, 1, 4, 24, 3, 1, 1, 0), 'Wg', 'Wg igemm<128x32> WgALoader+WgBLoader slabs=', True),
+    ((2, 1, 12, 4, 3, 1, 1, 0), 'Wg', 'Wg igemm<128x32> WgALoaderRow+WgBLoaderRow slabs=', False),
+    ((3, 1, 6, 16, 3, 1, 1, 0), 'Wg', 'Wg igemm<128x32> WgALoaderRow+WgBLoaderRow slabs=', True),
+    ((2, 3, 6, 4, 65, 4, 2, 1), 'Wg', 'Wg igemm<128x64> WgALoader+WgBLoader slabs=', False),
+    ((3, 4, 4, 24, 65, 3, 1, 1), 'Wg', 'Wg igemm<128x64> WgALoader+WgBLoader slabs=', True),
+    ((2, 4, 12, 4, 65, 3, 1, 1), 'Wg', 'Wg igemm<128x64> WgALoaderRow+WgBLoaderRow slabs=', False),
+    ((3, 4, 6, 16, 65, 3, 1, 1), 'Wg', 'Wg igemm<128x64> WgALoaderRow+WgBLoaderRow slabs=', True),
+    ((2, 3, 6, 4, 3, 4, 2, 1), 'Wg', 'Wg igemm<64x64> WgALoader+WgBLoader slabs=', False),
+    ((3, 4, 4, 24, 3, 3, 1, 1), 'Wg', 'Wg igemm<64x64> WgALoader+WgBLoader slabs=', True),
+    ((2, 4, 12, 4, 3, 3, 1, 1), 'Wg', 'Wg igemm<64x64> WgALoaderRow+WgBLoaderRow slabs=', False),
+    ((3, 4, 6, 16, 3, 3, 1, 1), 'Wg', 'Wg igemm<64x64> WgALoaderRow+WgBLoaderRow slabs=', True),
+    # second row of its key: ConvFwdALoaderRow4 on a tall map (whole tiles: no mid-tile shape exists)
+    ((1, 1, 48, 32, 3, 4, 2, 1), 'F', 'F igemm<128x32> ConvFwdALoaderRow4 slabs= bn_stats_rows=', False),
+    # second row of its key: 12-pixel rows of the per-phase grid, which ConvDgALoaderRow4 took until this table found that a
+    # tile starting inside such a row (64 % 12 != 0) reads its first pixel's left neighbour from outside the tile
+    ((3, 64, 4, 24, 3, 4, 2, 1), 'Dg', 'Dg igemm<64x64> ConvDgALoader splits= bn_stats_rows=', False),
+]
+RECT_ROWS = [(RectCase(*sh), op, form, split) for sh, op, form, split in _RECT_TABLE]
+# keys of _CONV_TABLE that no rectangle of the enumeration reaches (tests/test_exact_cases.py asserts that it does not)
+RECT_UNREACHED = []
+
+# conv3d on boxes that are no cubes: one row per form enumerate_box_plans() reaches (tools/find_exact_cases.py --box) -- the
+# 13 forms of _CONV3_TABLE and 7 that no cube of it reaches (F igemm<128x128 | 128x64 | 64x64> Conv3DFwdALoader, F igemm
+# <128x64 | 128x128> Conv3DFwdALoaderTap, Dg igemm<128x128> Conv3DDgALoader, Wg igemm<128x32>).  D, H, W are pairwise
+# different in every row, and every row is mid-tile (BOX3_MID_FORMS of BOX3_FORMS).
+BOX3_FORMS, BOX3_MID_FORMS = 20, 20
+_BOX3_TABLE = [
+    ((2, 128, 4, 6, 8, 20), 'Dg', 'Dg igemm2<256x128> Conv3DDgTapA2(gather, LDS-DMA 4B) splits= slabs='),
+    ((24, 130, 6, 10, 12, 8), 'Dg', 'Dg igemm<128x128> Conv3DDgALoader splits= slabs='),
+    ((2, 1, 4, 6, 8, 8), 'Dg', 'Dg igemm<128x32> Conv3DDgALoader splits= slabs='),
+    ((24, 72, 6, 10, 12, 8), 'Dg', 'Dg igemm<128x64> Conv3DDgALoader splits= slabs='),
+    ((2, 64, 4, 6, 8, 8), 'Dg', 'Dg igemm<64x64> Conv3DDgALoader splits= slabs='),
+    ((64, 16, 6, 10, 32, 512), 'F', 'F igemm2<256x128> Conv3DTapA2(gather, LDS-DMA 4B) splits= slabs='),
+    ((64, 16, 4, 10, 24, 512), 'F', 'F igemm2<256x64> Conv3DTapA2(gather, LDS-DMA 4B) splits= slabs='),
+    ((64, 1, 6, 24, 32, 72), 'F', 'F igemm<128x128> Conv3DFwdALoader splits= slabs='),
+    ((64, 16, 6, 24, 32, 72), 'F', 'F igemm<128x128> Conv3DFwdALoaderTap splits= slabs='),
+    ((2, 1, 4, 6, 8, 8), 'F', 'F igemm<128x32> Conv3DFwdALoader splits= slabs='),
+    ((2, 16, 4, 6, 8, 8), 'F', 'F igemm<128x32> Conv3DFwdALoaderTap splits= slabs='),
+    ((64, 1, 6, 12, 32, 72), 'F', 'F igemm<128x64> Conv3DFwdALoader splits= slabs='),
+    ((64, 16, 6, 12, 32, 72), 'F', 'F igemm<128x64> Conv3DFwdALoaderTap splits= slabs='),
+    ((2, 1, 4, 6, 8, 64), 'F', 'F igemm<64x64> Conv3DFwdALoader splits= slabs='),
+    ((2, 16, 4, 6, 8, 64), 'F', 'F igemm<64x64> Conv3DFwdALoaderTap splits= slabs='),
+    ((2, 1, 4, 6, 8, 128), 'Wg', 'Wg igemm2r<128x256> WgALoader+Wg3DBLoader(register-staged) splits= slabs='),
+    ((2, 1, 4, 6, 8, 512), 'Wg', 'Wg igemm2r<256x128> WgALoader+Wg3DBLoader(register-staged) splits= slabs='),
+    ((2, 4, 4, 6, 8, 72), 'Wg', 'Wg igemm<128x128> WgALoader+Wg3DBLoader splits= slabs='),
+    ((2, 1, 4, 6, 8, 8), 'Wg', 'Wg igemm<128x32> WgALoader+Wg3DBLoader splits= slabs='),
+    ((2, 4, 4, 6, 8, 8), 'Wg', 'Wg igemm<64x64> WgALoader+Wg3DBLoader splits= slabs='),
+]
+BOX3_ROWS = [(Box3Case(*c), op, form) for c, op, form in _BOX3_TABLE]
+BOX3_UNREACHED = []
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -551,6 +951,18 @@ STATS_CASES = [ConvCase(N, C, H, K, 4, 2, 1) for (N, C, H, K) in
                 (128, 64, 32, 128), (37, 24, 16, 72)]]
 
 
+# the same on rectangular maps, each list with a tall, a wide and a mid-tile shape (24, 96, 80, 160, 192 and 384 pixels
+# per image, N > 1)
+RECT_SPLIT_K_CASES = [RectCase(50, 512, 4, 6, 512, 3, 1, 1), RectCase(16, 96, 12, 8, 200, 3, 1, 1),
+                      RectCase(50, 256, 8, 12, 512, 5, 2, 2), RectCase(3, 256, 12, 8, 512, 4, 2, 1),
+                      RectCase(3, 512, 6, 4, 512, 1, 1, 0)]
+RECT_UNALIGNED_CASES = [RectCase(128, 64, 48, 32, 128, 4, 2, 1), RectCase(50, 16, 10, 32, 1024, 4, 2, 1)]
+RECT_EXTRA_ROWS = [(c, op) for c in RECT_SPLIT_K_CASES + RECT_UNALIGNED_CASES for op in OPS]
+RECT_STATS_CASES = [RectCase(N, C, H, W, K, 4, 2, 1) for (N, C, H, W, K) in
+                    [(3, 3, 24, 16, 5), (4, 8, 16, 24, 16), (3, 20, 12, 8, 40), (8, 64, 24, 16, 128), (16, 32, 48, 32, 96),
+                     (50, 16, 48, 32, 256), (50, 128, 10, 64, 64), (50, 128, 48, 16, 64), (37, 24, 12, 16, 72)]]
+
+
 def extra_id(row):
     return "%s-%s" % (row[1], case_id(row[0]))
 
@@ -559,10 +971,10 @@ def extra_id(row):
 def stats_reference(c_key, op):
     """Operands thin enough for the sums of the BatchNorm epilogue: (a, b, y64) with the per-channel sum over ALL pixels
     of y^2 (hence of every partial row, and of |y|) below 2^24 -- thinned until it is."""
-    c = ConvCase(*c_key)
+    c = conv_case(c_key)
     set_threads()
-    OH = out_side(c.H, c.k, c.s, c.p)
-    shape_a = (c.N, c.C, c.H, c.H) if op == "F" else (c.N, c.K, OH, OH)
+    (H, W), (OH, OW) = map_sides(c)
+    shape_a = (c.N, c.C, H, W) if op == "F" else (c.N, c.K, OH, OW)
     for step, density in enumerate((1.0, 0.5, 0.25, 0.12, 0.06, 0.03, 0.015, 0.008, 0.004)):
         a = int_operands(shape_a, 3, density, 7000 + step)
         b = int_operands((c.K, c.C, c.k, c.k), 1, density, 7100 + step)
@@ -608,17 +1020,26 @@ def act64(t, name):
 
 DGRAD_ACT_CASES = [(4, 3, 64, 16), (128, 3, 64, 64), (3, 4, 32, 40)]            # (N, C, H, K), k4 s2 p1
 WGRAD_ACT_CASES = [(16, 3, 64, 64), (20, 4, 64, 32), (128, 3, 64, 64)]
+# the same on rectangular maps, (N, C, H, W, K): tall, wide and mid-tile (N > 1, H/2 * W/2 neither divides 256 nor is a
+# multiple of it: 384, 96 and 12 pixels; 384 and 144) shapes at which gz_conv2d_dgrad_act_fuses / _wgrad_act_fuses say yes
+RECT_DGRAD_ACT_CASES = [(2, 3, 48, 32, 16), (4, 3, 48, 64, 16), (3, 4, 24, 16, 40), (5, 3, 6, 8, 16), (24, 4, 48, 64, 32)]
+RECT_WGRAD_ACT_CASES = [(50, 3, 48, 32, 64), (128, 4, 6, 96, 16), (24, 4, 48, 64, 32), (50, 4, 48, 32, 32)]
+
+
+def act_case_shape(case):
+    """(N, C, H, W, K) of a (N, C, H, K) or (N, C, H, W, K) case of the two tables above."""
+    return tuple(case) if len(case) == 5 else (case[0], case[1], case[2], case[2], case[3])
 
 
 @functools.lru_cache(maxsize=2)
 def dgrad_act_case(case, name):
     """d/dx of act(conv(x, w) + b): (x, w, b, gy, y64, dx64).  The masked gradient holds multiples of the slope, so the
     bound is 2^24 * slope."""
-    N, C, H, K = case
+    N, C, H, W, K = act_case_shape(case)
     slope = SLOPES[name]
     set_threads()
-    x, w, b = int_operands((N, C, H, H), 3, 1.0, 1), int_operands((K, C, 4, 4), 1, 1.0, 2), int_operands((K,), 7, 1.0, 3)
-    gy = int_operands((N, K, H // 2, H // 2), WIDE, 1.0, 4)
+    x, w, b = int_operands((N, C, H, W), 3, 1.0, 1), int_operands((K, C, 4, 4), 1, 1.0, 2), int_operands((K,), 7, 1.0, 3)
+    gy = int_operands((N, K, H // 2, W // 2), WIDE, 1.0, 4)
     y = act64(TF.conv2d(x.double(), w.double(), b.double(), 2, 1), name)
     g_pre = gy.double() * torch.where(y > 0, 1.0, slope).double()
     assert_exact_precondition(TF.conv_transpose2d(g_pre.abs(), w.double().abs(), None, 2, 1) / (slope or 1.0), "dgrad_act")
@@ -628,13 +1049,13 @@ def dgrad_act_case(case, name):
 @functools.lru_cache(maxsize=2)
 def wgrad_act_case(case, name):
     """Weight and bias gradient of act(conv(x, w) + b) over two batches: (xs, gys, w, b, dw64, db64)."""
-    N, C, H, K = case
+    N, C, H, W, K = act_case_shape(case)
     slope = SLOPES[name]
     set_threads()
-    d, amp = thin(2 * N * (H // 2) ** 2)
+    d, amp = thin(2 * N * (H // 2) * (W // 2))
     w0, b0 = int_operands((K, C, 4, 4), 1, 1.0, 12), int_operands((K,), 7, 1.0, 13)
-    xs = [int_operands((N, C, H, H), WIDE, d, 10 + i) for i in (0, 100)]
-    gys = [int_operands((N, K, H // 2, H // 2), amp, d, 11 + i) for i in (0, 100)]
+    xs = [int_operands((N, C, H, W), WIDE, d, 10 + i) for i in (0, 100)]
+    gys = [int_operands((N, K, H // 2, W // 2), amp, d, 11 + i) for i in (0, 100)]
     dw_ref, db_ref, dw_abs = 0, 0, 0
     for x, gy in zip(xs, gys):
         y = act64(TF.conv2d(x.double(), w0.double(), b0.double(), 2, 1), name)

@@ -47,7 +47,7 @@ def _run_conv(c, op, a, b, bias=None, act=None, slope=0.0):
     if op == "F":
         return F._conv_fwd_raw(a, b, bias, _geom(c), act, slope)
     if op == "Dg":
-        return F._conv_dgrad_raw(a, b, bias, _geom(c), (c.H, c.H), act, slope)
+        return F._conv_dgrad_raw(a, b, bias, _geom(c), S.map_sides(c)[0], act, slope)
     assert bias is None and act == F.ACT_NONE
     return F._conv_wgrad_raw(a, b, _geom(c))
 
@@ -281,6 +281,188 @@ def test_conv3d_family(row):
         fn = F._conv3d_fwd_raw if op == "F" else F._conv3d_dgrad_raw
         assert_bits_equal(fn(ad, bd, bias.cuda(), F.ACT_RELU, 0.0), torch.relu(ref + bias.double().view(1, -1, 1, 1, 1)),
                           "bias + relu")
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# d2. rectangular maps (H != W) and box volumes: the same launches where an image boundary falls inside a tile, H is not
+# W and a vertical halo row is not the neighbouring image's (tests/exact_support.py, RECT_ROWS / BOX3_ROWS)
+# ---------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("row", S.RECT_ROWS, ids=S.row_id)
+def test_conv2d_rectangular_at_every_plan_form(row):
+    c, op, form, split = row
+    text = S.conv2d_plan(op, *c)
+    assert S.plan_form(text) == form, "the case moved off its kernel: " + text
+    a, b, ref = S.conv_ref(c, op)
+    assert_bits_equal(_run_conv(c, op, a.cuda(), b.cuda()), ref, "%s  [%s]" % (S.row_id(row), text))
+
+
+def _epilogue_group(row):
+    """(direction, loader family) of a row; the direct kernels by their own names."""
+    form = row[2]
+    fam = S.loader_family(form)
+    return row[1], form.split(" direct ")[1].split("<")[0] if fam == "direct" else fam
+
+
+def _rect_epilogue_rows():
+    """The cheapest rectangular row of every loader family (and of every direct kernel) in the two directions that have
+    an epilogue."""
+    best = {}
+    for row in S.RECT_ROWS:
+        if row[1] != "Wg" and "ConvDg5A2" not in row[2]:      # (ConvDg5A2 hands a launch with an epilogue to ConvDgTapA2)
+            g = _epilogue_group(row)
+            if g not in best or S.case_macs(row[0]) < S.case_macs(best[g][0]):
+                best[g] = row
+    return [best[g] for g in sorted(best)]
+
+
+RECT_EPILOGUE_ROWS = _rect_epilogue_rows()
+
+
+def test_the_rectangular_epilogue_rows_are_all_there():
+    # F: ConvFwdA2, ConvTapA2, Row4, K4V, Tap, the plain loader, two direct kernels; Dg: ConvDgA2, ConvDgTapA2, Row4, Tap, the
+    # plain loader, four direct kernels
+    assert len(RECT_EPILOGUE_ROWS) == 17
+    assert any(r[0].H > r[0].W for r in RECT_EPILOGUE_ROWS) and any(r[0].H < r[0].W for r in RECT_EPILOGUE_ROWS)
+
+
+@pytest.mark.parametrize("row", RECT_EPILOGUE_ROWS, ids=S.row_id)
+def test_conv2d_rectangular_bias_and_activation_epilogues(row):
+    test_conv2d_bias_and_activation_epilogues(row)
+
+
+@pytest.mark.parametrize("case", S.RECT_STATS_CASES, ids=S.case_id)
+@pytest.mark.parametrize("op", ["F", "Dg"])
+def test_rectangular_batchnorm_statistics_epilogue(case, op):
+    """test_batchnorm_statistics_epilogue's assertions on rectangular maps: which rows of an image a partial row of the
+    statistics owns is where H and W part ways."""
+    F = _F()
+    c = case
+    fn = F.conv2d_with_stats if op == "F" else F.conv_transpose2d_with_stats
+    a, b, ref = S.conv_ref(c, op)
+    y, stats = fn(a.cuda(), b.cuda(), _geom(c))
+    assert_bits_equal(y, ref, "output (wide operands)")
+    a, b, y64 = S.stats_reference(tuple(c), op)
+    y, stats = fn(a.cuda(), b.cuda(), _geom(c))
+    assert_bits_equal(y, y64, "output (thin operands)")
+    rows = getattr(_lib()[0], "gz_conv2d_fwd_stats_rows" if op == "F" else "gz_conv2d_dgrad_stats_rows")(
+        c.N, c.C, c.H, c.W, c.K, c.H // 2, c.W // 2, 4, 4, 2, 1)
+    assert rows > 0, "the case no longer carries the statistics"
+    assert tuple(stats.shape) == (rows, y64.shape[1], 2)
+    assert torch.equal(stats, stats.round()) and bool((stats[:, :, 1] >= stats[:, :, 0].abs()).all())
+    tot = stats.double().sum(0).cpu()
+    assert_bits_equal(tot[:, 0], y64.sum((0, 2, 3)), "sum y")
+    assert_bits_equal(tot[:, 1], (y64 * y64).sum((0, 2, 3)), "sum y^2")
+
+
+@pytest.mark.parametrize("case", S.RECT_DGRAD_ACT_CASES)
+@pytest.mark.parametrize("name", ["relu", "lrelu0.5", "lrelu0.25"])
+def test_rectangular_input_gradient_with_the_activation_mask_formed_on_load(case, name):
+    F = _F()
+    lib, _ = _lib()
+    N, C, H, W, K = case
+    act, slope = _act_args(name)
+    assert lib.gz_conv2d_dgrad_act_fuses(N, C, H, W, K, H // 2, W // 2, 4, 4, 2, 1, act)
+    x, w, b, gy, y, ref = S.dgrad_act_case(case, name)
+    xd = x.cuda().requires_grad_()
+    out = F.conv2d(xd, w.cuda(), b.cuda(), F.K4S2P1, act, slope)
+    assert_bits_equal(out, y, "forward")
+    out.backward(gy.cuda())
+    assert_bits_equal(xd.grad, ref, "dgrad_act %s %s" % (case, name))
+
+
+@pytest.mark.parametrize("case", S.RECT_WGRAD_ACT_CASES)
+@pytest.mark.parametrize("name", ["relu", "lrelu0.5", "lrelu0.25"])
+def test_rectangular_weight_and_bias_gradient_with_the_activation_mask_formed_on_load(case, name):
+    """gz_conv2d_wgrad_act_partial through the sinks, two batches before one flush."""
+    F = _F()
+    lib, _ = _lib()
+    N, C, H, W, K = case
+    act, slope = _act_args(name)
+    assert lib.gz_conv2d_wgrad_act_fuses(N, C, H, W, K, H // 2, W // 2, 4, 4, 2, 1, act) == 1
+    xs, gys, w0, b0, dw_ref, db_ref = S.wgrad_act_case(case, name)
+    w, b = torch.nn.Parameter(w0.cuda()), torch.nn.Parameter(b0.cuda())
+    prev = F.set_grad_sinks(True)
+    try:
+        for x, gy in zip(xs, gys):
+            F.conv2d(x.cuda(), w, b, F.K4S2P1, act, slope).backward(gy.cuda())
+        assert w.grad is None and b.grad is None
+        F.flush_grad_sinks()
+    finally:
+        F.set_grad_sinks(*prev)
+    assert_bits_equal(w.grad, dw_ref, "dw")
+    assert_bits_equal(b.grad, db_ref, "db")
+
+
+RECT_WG_BIAS_ROWS = [r for r in S.RECT_ROWS if r[1] == "Wg" and S.conv_terms(r[0], "Wg") * r[0].K < 3e7]
+
+
+@pytest.mark.parametrize("row", RECT_WG_BIAS_ROWS, ids=S.row_id)
+def test_rectangular_weight_gradient_with_the_bias_gradient(row):
+    test_weight_gradient_with_the_bias_gradient(row)
+
+
+def test_some_rectangular_weight_gradient_case_fuses_its_bias_gradient():
+    lib, _ = _lib()
+    fused = []
+    for c, _, _, _ in RECT_WG_BIAS_ROWS:
+        (H, W), (OH, OW) = S.map_sides(c)
+        if lib.gz_conv2d_wgrad_fuses_bias(c.N, c.C, H, W, c.K, OH, OW, c.k, c.k, c.s, c.p) == 1:
+            fused.append(c)
+    assert fused, "no rectangular exact case takes the fused bias gradient"
+
+
+def _rect_sink_rows():
+    """The cheapest rectangular weight-gradient row of every loader family and direct kernel, and of each family the
+    split and the unsplit launch where the table has both below 3e9 multiply-adds (the test takes three fp64 passes)."""
+    best = {}
+    for row in S.RECT_ROWS:
+        if row[1] == "Wg" and S.case_macs(row[0]) < 3e9:
+            g = _epilogue_group(row) + (row[3],)
+            if g not in best or S.case_macs(row[0]) < S.case_macs(best[g][0]):
+                best[g] = row
+    return [best[g] for g in sorted(best)]
+
+
+RECT_SINK_ROWS = _rect_sink_rows()
+
+
+def test_the_rectangular_sink_rows_are_all_there():
+    # direct: fewk, fewc, smallch (split); WgImgBG, WgALoaderRow, WgALoader: split and unsplit; igemm2r, WgImgB2: unsplit
+    assert len(RECT_SINK_ROWS) == 11 and any(r[3] for r in RECT_SINK_ROWS) and any(not r[3] for r in RECT_SINK_ROWS)
+    assert any(r[0].H > r[0].W for r in RECT_SINK_ROWS) and any(r[0].H < r[0].W for r in RECT_SINK_ROWS)
+
+
+@pytest.mark.parametrize("row", RECT_SINK_ROWS, ids=S.row_id)
+def test_rectangular_weight_gradient_slabs_summed_by_reduce_multi(row):
+    test_weight_gradient_slabs_summed_by_reduce_multi(row)
+
+
+@pytest.mark.parametrize("case", S.RECT_SPLIT_K_CASES, ids=S.case_id)
+def test_rectangular_conv_split_k(case):
+    lib, _ = _lib()
+    c = case
+    (H, W), (OH, OW) = S.map_sides(c)
+    assert lib.gz_conv2d_fwd_workspace_bytes(c.N, c.C, H, W, c.K, OH, OW, c.k, c.k, c.s, c.p) > 0, "case no longer splits"
+    assert lib.gz_conv2d_dgrad_workspace_bytes(c.N, c.C, H, W, c.K, OH, OW, c.k, c.k, c.s, c.p) > 0
+    for op, nb in (("F", c.K), ("Dg", c.C)):
+        a, b, ref = S.conv_ref(c, op)
+        bias = int_operands((nb,), 7, 1.0, 43)
+        assert_exact_precondition(S.conv_apply(c, op, a.double().abs(), b.double().abs()) + 7.0, op)
+        assert_bits_equal(_run_conv(c, op, a.cuda(), b.cuda()), ref, op)
+        assert_bits_equal(_run_conv(c, op, a.cuda(), b.cuda(), bias.cuda(), *_act_args("lrelu0.5")),
+                          _act64(ref + bias.double().view(1, -1, 1, 1), "lrelu0.5"), op + " bias + lrelu0.5")
+    a, b, ref = S.conv_ref(c, "Wg")
+    assert_bits_equal(_run_conv(c, "Wg", a.cuda(), b.cuda()), ref, "Wg  [%s]" % S.conv2d_plan("Wg", *c))
+
+
+@pytest.mark.parametrize("row", [r for r in S.RECT_EXTRA_ROWS if r[0] in S.RECT_UNALIGNED_CASES], ids=S.extra_id)
+def test_rectangular_conv_operands_four_bytes_off_alignment(row):
+    test_conv_operands_four_bytes_off_alignment(row)
+
+
+@pytest.mark.parametrize("row", S.BOX3_ROWS, ids=S.row3_id)
+def test_conv3d_box_at_every_plan_form(row):
+    test_conv3d_family(row)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
