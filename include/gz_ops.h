@@ -539,6 +539,37 @@ int gz_u8hwc_gather_to_nchw(const unsigned char* set, long long M, const long lo
 int gz_diffaug(const float* x0, const float* x1, const float* params, float* y, int R0, int R1, int C, int H, int W,
                int cut_h, int cut_w, int mode, hipStream_t stream);
 
+/* ---- adaptive discriminator augmentation (Karras et al. 2020; csrc/gz_ada.hip) ------------------
+ * gz_diffaug with a gate per sample and group and the two pixel-blitting transforms.  params is [R0 + R1, 16]:
+ *   0..6   b, s, c, th, tw, h0, w0 as for gz_diffaug
+ *   7      orientation code o = k + 4 f: f = x-flip bit, k = number of torch.rot90(., k, dims=[2, 3]) turns applied
+ *          after the flip.  Clamped to [0, 7] (NaN: 0) and masked by `blit` (bit 0: x-flip permitted, bit 1: rot90
+ *          permitted) inside the kernel
+ *   8..12  uniforms in [0, 1) for the gates of color, translation, cutout, xflip, rot90
+ *   13..15 zero (not read)
+ * A group is ON iff p == NULL or u_group < p[0] (p: a device scalar).  Color off: the element passes through as
+ * loaded, no colour arithmetic.  Translation off: shift (0, 0).  Cutout off: no box.  Xflip off or not permitted:
+ * f = 0.  Rot90 off or not permitted: k = 0.  At p[0] = 0 all three modes return the input bits.
+ *   A' = Mask . Shift . Q . Con . Sat,  Q x = rot90(flip_w(x) if f else x, k)  (a permutation commuting with Con . Sat)
+ * mode 0: A' x + k; mode 1: A' x; mode 2: A'^T x = Con . Sat . Q^T . Shift^T . Mask x.  Sources, y, stacking, overlap
+ * rule, alignment freedom and error codes as for gz_diffaug.  One launch, no workspace, no atomics.  The elements of
+ * a sample are loaded in row-contiguous runs whatever the orientation and placed at their permuted positions in an
+ * LDS plane (pitch W + 1 when k is odd), one channel at a time; samples with k even and no flip skip the staging.
+ * The mean is a fixed-order reduction whose longest chain of dependent additions is 30.
+ * Supported: the shapes of gz_diffaug; with bit 1 of blit set additionally H == W <= 128 (the staged plane of
+ * H (W + 1) floats lives in LDS).  Anything else returns GZ_ERR_UNSUPPORTED and launches nothing.
+ * GZ_ERR_BAD_SHAPE: as for gz_diffaug, or blit outside 0..3. */
+int gz_diffaug_gated(const float* x0, const float* x1, const float* params, const float* p, float* y, int R0, int R1,
+                     int C, int H, int W, int cut_h, int cut_w, int blit, int mode, hipStream_t stream);
+/* The ADA controller.  state = four device floats {sum_sign, count, p, last_r}; nothing synchronises with the host.
+ * gz_ada_observe: state[0] += sum_i sign(logits[i]), sign = (x > 0) - (x < 0) (NaN and +-0 contribute 0);
+ *   state[1] += n.  One workgroup, fixed order: exact integers in fp32 below 2^24.
+ * gz_ada_update: if state[1] > 0: r = state[0] / state[1]; p = min(max(p + step * sgn(r - target), 0), 1);
+ *   state[3] = r; state[0] = state[1] = 0.  Otherwise nothing changes.
+ * GZ_ERR_BAD_SHAPE: a null pointer, n < 1, a non-finite or negative step, a non-finite target. */
+int gz_ada_observe(const float* logits, int n, float* state, hipStream_t stream);
+int gz_ada_update(float* state, float target, float step, hipStream_t stream);
+
 /* ---- fused multi-tensor optimizer steps (the `optimiser` nodes of conf/expt/<name>.yaml) -------------------------
  * `count` <= GZ_OPT_MAX_TENSORS tensors per call (host arrays of device pointers and element counts);
  * grads are multiplied by grad_scale first (1/world for data-parallel means).  Formulas are torch.optim's

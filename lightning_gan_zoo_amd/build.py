@@ -27,7 +27,7 @@ DIGEST_SOURCE = "gz_build_id.hip"          # holds gz_source_digest(); compiled 
 SOURCES = ["gz_conv_fwd.hip", "gz_conv_dgrad.hip", "gz_conv_wgrad.hip", "gz_conv3d.hip", "gz_conv_direct.hip",
            "gz_conv_fwd_igemm.hip", "gz_conv.hip", "gz_pack.hip", "gz_norm.hip", "gz_misc.hip", "gz_resample.hip", "gz_optim.hip",
            "gz_resnet.hip", "gz_loss.hip", "gz_infer.hip", "gz_figures.hip", "gz_ema.hip", "gz_kid.hip", "gz_moments.hip",
-           "gz_sqrtm.hip", "gz_inception_score.hip", "gz_prdc.hip", "gz_diffaug.hip", "gz_swd.hip"]
+           "gz_sqrtm.hip", "gz_inception_score.hip", "gz_prdc.hip", "gz_diffaug.hip", "gz_swd.hip", "gz_ada.hip"]
 FLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-I", INCLUDE]
 
 

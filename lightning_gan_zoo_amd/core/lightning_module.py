@@ -15,7 +15,7 @@ import torch
 
 from .. import functional as F
 from ..config import instantiate
-from ..augment import DiffAugment
+from ..augment import build_augment
 from ..harness import LightningModule, draw_on_host
 from .utils.utils import VerboseShapeExecution, compute_grad2, gradient_penalty
 
@@ -76,7 +76,8 @@ class BaseGAN(LightningModule):
         self.fixed_noise = self.noise_distn.sample((8, cfg.model.noise_dim))
         # DiffAugment of every tensor handed to the discriminator (augment.py; runner key `diffaugment`): None = off,
         # and then every site below is the code it was before the key existed -- no launch, no host draw
-        self.diffaugment = DiffAugment(cfg.get("diffaugment", "")) or None
+        # (augment_blit / augment_p / ada_target set: an AdaptiveAugment, csrc/gz_ada.hip; else DiffAugment itself)
+        self.diffaugment = build_augment(cfg) or None
         if cfg.debug.verbose_shape:                      # reference :53-54
             self.apply(VerboseShapeExecution)
 
@@ -97,6 +98,13 @@ class BaseGAN(LightningModule):
     def augmented(self, x):
         """``x`` as the discriminator sees it: through DiffAugment with parameters drawn at this call, or ``x`` itself."""
         return x if self.diffaugment is None else self.diffaugment(x)
+
+    def observe_real(self, real_logits):
+        """A discriminator step hands its logits of the real batch to the ADA controller (augment.AdaptiveAugment
+        .observe: device-side accumulation, no read-back); nothing happens unless ``ada_target`` is set."""
+        observe = getattr(self.diffaugment, "observe", None)
+        if observe is not None:
+            observe(real_logits.detach())
 
     def stacked_batch(self, real, fake):
         """[real; fake.detach()]: the concatenation, or -- augmenting -- ONE two-source launch that writes
@@ -194,6 +202,7 @@ class DCGAN(BaseGAN):
                 fake = self.generator(noise)
                 logits = self.stacked_discriminator(real, fake)
                 if logits is not None:
+                    self.observe_real(logits[:len(real)])
                     loss_disc = F.bce_logits_pair_mean(logits, 1.0, 0.0)      # (BCE(real, 1) + BCE(fake, 0)) / 2
                     self.log("train/d_loss", loss_disc)
                     return loss_disc
@@ -204,6 +213,7 @@ class DCGAN(BaseGAN):
             else:
                 fake = self.generator(noise)
                 disc_real = self.discriminator(self.augmented(real)).reshape(-1)
+            self.observe_real(disc_real)
             loss_disc_real = self.criterion_const(disc_real, 1.0)
             disc_fake = self.discriminator(self.augmented(fake.detach())).reshape(-1)
             loss_disc_fake = self.criterion_const(disc_fake, 0.0)
@@ -229,6 +239,7 @@ class GANStabilityR1(BaseGAN):
         if optimizer_idx == 0:
             real.requires_grad_()
             disc_real = self.discriminator(self.augmented(real)).reshape(-1)
+            self.observe_real(disc_real)
             loss_disc_real = self.criterion_const(disc_real, 1.0)
             disc_fake = self.discriminator(self.augmented(fake.detach())).reshape(-1)
             loss_disc_fake = self.criterion_const(disc_fake, 0.0)
@@ -260,6 +271,7 @@ class WGAN(BaseGAN):
                 fake = self.generator(noise)
                 logits = self.stacked_discriminator(real, fake)
                 if logits is not None:
+                    self.observe_real(logits[:len(real)])      # (a fixed augment_p only: ada_target is refused here)
                     loss_disc = F.weighted_half_means(logits, -1.0, 1.0)      # -(mean(D(real)) - mean(D(fake)))
                     self.log("train/d_loss", loss_disc)
                     return loss_disc
@@ -270,6 +282,7 @@ class WGAN(BaseGAN):
             else:
                 fake = self.generator(noise)
                 disc_real = self.discriminator(self.augmented(real)).reshape(-1)
+            self.observe_real(disc_real)
             disc_fake = self.discriminator(self.augmented(fake.detach())).reshape(-1)
             loss_disc = -(torch.mean(disc_real) - torch.mean(disc_fake))
             self.log("train/d_loss", loss_disc)
@@ -308,6 +321,7 @@ class WGANGP(BaseGAN):
             else:
                 fake = self.generator(noise)
                 disc_real = self.discriminator(self.augmented(real)).reshape(-1)
+            self.observe_real(logits[:len(real)] if logits is not None else disc_real)
             if logits is None:
                 disc_fake = self.discriminator(self.augmented(fake.detach())).reshape(-1)
             # `fake` is NOT detached here, as in the reference (:195-196)
@@ -347,6 +361,7 @@ class HOLOGAN(BaseGAN):
                 fake = self.generator(z)
                 if real.shape == fake.shape:
                     logits, d_z_pred = d(self.stacked_batch(real, fake), groups=2)
+                    self.observe_real(logits.reshape(-1)[:len(real)])
                     loss_disc = F.bce_logits_pair_mean(logits, 1.0, 0.0)       # (BCE(real, 1) + BCE(fake, 0)) / 2
                     q_loss = F.mse_mean(d_z_pred[len(real):], z)
                     self.log("train/d_loss", loss_disc)
@@ -362,6 +377,7 @@ class HOLOGAN(BaseGAN):
             else:
                 fake = self.generator(z)
                 disc_real, _ = self.discriminator(self.augmented(real))
+            self.observe_real(disc_real)
             loss_disc_real = self.criterion_const(disc_real, 1.0)
             disc_fake, d_z_pred = self.discriminator(self.augmented(fake.detach()))
             loss_disc_fake = self.criterion_const(disc_fake, 0.0)

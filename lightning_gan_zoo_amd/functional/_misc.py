@@ -563,4 +563,102 @@ def diffaugment(x, params, cut, x1=None):
     return _DiffAug.apply(x, x1, params, (int(cut[0]), int(cut[1])), True)
 
 
+# ---------------------------------------------------------------------------
+# Adaptive discriminator augmentation (csrc/gz_ada.hip; DESIGN.md 3.5.5): DiffAugment with a gate per sample and group
+# and the orientation Q (x-flip, rot90).  A' = Mask . Shift . Q . Con . Sat is linear once the parameters are drawn, so
+# the pair below closes under differentiation exactly as _DiffAug / _DiffAugT do.
+# ---------------------------------------------------------------------------
+def _diffaug_gated_raw(x, x1, params, cut, p, blit, mode):
+    x, params = _req(x, "x"), _req(params, "params")
+    if x.dim() != 4:
+        raise RuntimeError("lightning_gan_zoo_amd: expected an NCHW tensor, got shape %s" % (tuple(x.shape),))
+    R0, C, H, W = x.shape
+    R1 = 0
+    if x1 is not None:
+        x1 = _req(x1, "x1")
+        if x1.dim() != 4 or x1.shape[1:] != x.shape[1:]:
+            raise RuntimeError("lightning_gan_zoo_amd: diffaugment sources differ in shape: %s and %s"
+                               % (tuple(x.shape), tuple(x1.shape)))
+        R1 = x1.shape[0]
+    if tuple(params.shape) != (R0 + R1, 16):
+        raise RuntimeError("lightning_gan_zoo_amd: gated diffaugment params must be [%d, 16], got %s"
+                           % (R0 + R1, tuple(params.shape)))
+    if p is not None:
+        p = _req(p, "p")
+        if p.numel() < 1:
+            raise RuntimeError("lightning_gan_zoo_amd: the gate probability must hold one float")
+    if (int(blit) & 2) and H != W:
+        raise RuntimeError("lightning_gan_zoo_amd: rot90 needs a square image, got %d x %d" % (H, W))
+    y = torch.empty((R0 + R1, C, H, W), device=x.device, dtype=torch.float32)
+    check(lib.gz_diffaug_gated(_p(x), _p(x1), _p(params), _p(p), _p(y), R0, R1, C, H, W, int(cut[0]), int(cut[1]),
+                               int(blit), mode, _stream()), "diffaug_gated")
+    return y
+
+
+class _DiffAugGated(torch.autograd.Function):
+    """[A' x + k; A' x1 + k] (affine) or [A' x; A' x1] -- gz_diffaug_gated modes 0 and 1."""
+
+    @staticmethod
+    def forward(ctx, x, x1, params, p, cut, blit, affine):
+        ctx.save_for_backward(params, *(() if p is None else (p,)))
+        ctx.cut, ctx.blit, ctx.r0 = cut, blit, x.shape[0]
+        return _diffaug_gated_raw(x, x1, params, cut, p, blit, 0 if affine else 1)
+
+    @staticmethod
+    def backward(ctx, g):
+        params, p = (ctx.saved_tensors + (None,))[:2]
+        r0, (need0, need1) = ctx.r0, ctx.needs_input_grad[:2]
+        g0 = g1 = None
+        if need0 and need1:                    # one adjoint launch over the stacked rows
+            gx = _DiffAugGatedT.apply(g, params, p, ctx.cut, ctx.blit)
+            g0, g1 = gx[:r0], gx[r0:]
+        elif need0:
+            g0 = _DiffAugGatedT.apply(g[:r0], params[:r0], p, ctx.cut, ctx.blit)
+        elif need1:
+            g1 = _DiffAugGatedT.apply(g[r0:], params[r0:], p, ctx.cut, ctx.blit)
+        return g0, g1, None, None, None, None, None
+
+
+class _DiffAugGatedT(torch.autograd.Function):
+    """A'^T g -- gz_diffaug_gated mode 2; its derivative with respect to g is A' again."""
+
+    @staticmethod
+    def forward(ctx, g, params, p, cut, blit):
+        ctx.save_for_backward(params, *(() if p is None else (p,)))
+        ctx.cut, ctx.blit = cut, blit
+        return _diffaug_gated_raw(g, None, params, cut, p, blit, 2)
+
+    @staticmethod
+    def backward(ctx, v):
+        params, p = (ctx.saved_tensors + (None,))[:2]
+        return _DiffAugGated.apply(v, None, params, p, ctx.cut, ctx.blit, False), None, None, None, None
+
+
+def diffaugment_gated(x, params16, cut, p, blit, x1=None):
+    """``diffaugment`` with gates and orientations: ``params16`` [R0 + R1, 16] = (b, s, c, th, tw, h0, w0, o, u_color,
+    u_translation, u_cutout, u_xflip, u_rot90, 0, 0, 0) with o = k + 4 f (f: x-flip, then k turns of torch.rot90); ``p``
+    a device float (a group is on iff its u < p) or None (all on); ``blit`` bit 0 permits the flip, bit 1 the turns.
+    The value of ``p`` is read by the kernel of each launch: a backward pass sees the p of its own time, so the tensor
+    must not change between a forward and its backward (augment.AdaptiveAugment hands each call its own copy).
+    Differentiable to any order in ``x`` / ``x1``; ``params16`` and ``p``
+    get no gradient."""
+    return _DiffAugGated.apply(x, x1, params16, p, (int(cut[0]), int(cut[1])), int(blit), True)
+
+
+def ada_observe(logits, state):
+    """state[0] += sum sign(logits), state[1] += len(logits) on the device (gz_ada_observe); no host read."""
+    logits, state = _req(logits, "logits"), _req(state, "state")
+    if state.numel() != 4:
+        raise RuntimeError("lightning_gan_zoo_amd: the ADA state is four floats {sum_sign, count, p, last_r}")
+    check(lib.gz_ada_observe(_p(logits), logits.numel(), _p(state), _stream()), "ada_observe")
+
+
+def ada_update(state, target, step):
+    """One controller update on the device (gz_ada_update): p moves by ``step`` toward r > target; no host read."""
+    state = _req(state, "state")
+    if state.numel() != 4:
+        raise RuntimeError("lightning_gan_zoo_amd: the ADA state is four floats {sum_sign, count, p, last_r}")
+    check(lib.gz_ada_update(_p(state), float(target), float(step), _stream()), "ada_update")
+
+
 __all__ = [n for n in list(globals()) if not n.startswith("__")]     # the flat namespace of the package (private helpers included)

@@ -64,6 +64,12 @@ RUNNER_KEYS = {"max_steps": None, "log_every": 10, "dataset_path": None, "seed":
                # DiffAugment of the discriminator's input (augment.py, csrc/gz_diffaug.hip): a comma-separated subset of
                # color, translation, cutout; "" = off.  Travels into the module's cfg as cfg.diffaugment
                "diffaugment": "",
+               # adaptive discriminator augmentation on top of it (augment.AdaptiveAugment, csrc/gz_ada.hip; Karras et
+               # al. 2020): augment_blit = a subset of xflip,rot90; augment_p = a fixed probability per sample and group
+               # (unset: 1.0, or the start value 0.0 when adapting); ada_target in (0, 1) = adapt p toward
+               # E[sign(D(real))] = target (the paper: 0.6), every ada_interval discriminator steps, at a rate that moves
+               # p from 0 to 1 over ada_kimg thousand real images.  All five travel into the module's cfg
+               "augment_blit": "", "augment_p": None, "ada_target": None, "ada_interval": 4, "ada_kimg": 500,
                # sliced Wasserstein distance on Laplacian-pyramid patches (eval.evaluate_swd, csrc/gz_swd.hip): a quality
                # number per resolution level from pixels alone -- no network, no weight file.  swd_images real and as many
                # generated images (clamped to the real images there are), swd_patches 7x7 patches per image and level,
@@ -104,6 +110,7 @@ def parse_overrides(argv):
         raise SystemExit("missing +expt=<dc_gan|wgan|wgan_gp|hologan|gan_stability_r1>")
     check_eval_keys(runner)
     check_diffaugment(runner)
+    check_ada_keys(runner, expt)
     return conf_dir, expt, rest, runner
 
 
@@ -114,6 +121,44 @@ def check_diffaugment(run):
         run["diffaugment"] = ",".join(parse_policy(run.get("diffaugment", "")))
     except ValueError as e:
         raise SystemExit(str(e)) from e
+
+
+ADA_KEYS = ("augment_blit", "augment_p", "ada_target", "ada_interval", "ada_kimg")
+
+
+def check_ada_keys(run, expt=None):
+    """The five keys of the adaptive augmentation: canonical augment_blit, ranges, and the combinations that make no
+    sense end the run with the reason."""
+    from .augment import parse_blit
+    try:
+        run["augment_blit"] = ",".join(parse_blit(run.get("augment_blit", "")))
+    except ValueError as e:
+        raise SystemExit(str(e)) from e
+
+    def number(key):
+        v = run.get(key)
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v):
+            raise SystemExit("%s must be a number, got %r" % (key, v))
+        return float(v)
+
+    if run.get("augment_p") is not None and not 0.0 <= number("augment_p") <= 1.0:
+        raise SystemExit("augment_p must lie in [0, 1], got %r" % (run["augment_p"],))
+    if run.get("ada_target") is not None and not 0.0 < number("ada_target") < 1.0:
+        raise SystemExit("ada_target must lie in (0, 1), got %r (the paper uses 0.6)" % (run["ada_target"],))
+    interval = run.get("ada_interval", 4)
+    if isinstance(interval, bool) or not isinstance(interval, int) or interval < 1:
+        raise SystemExit("ada_interval must be a positive integer, got %r" % (interval,))
+    if not number("ada_kimg") > 0:
+        raise SystemExit("ada_kimg must be positive, got %r" % (run["ada_kimg"],))
+    touched = [k for k in ADA_KEYS if run.get(k, RUNNER_KEYS[k]) != RUNNER_KEYS[k]]
+    if touched and not run.get("diffaugment") and not run["augment_blit"]:
+        raise SystemExit("%s set with nothing to apply: diffaugment and augment_blit are both empty; name at least one "
+                         "group (diffaugment=color,translation,cutout and / or augment_blit=xflip,rot90)"
+                         % ", ".join(touched))
+    if run.get("ada_target") is not None and expt in ("wgan", "wgan_gp"):
+        raise SystemExit("ada_target is not served for expt=%s: the controller reads the overfitting heuristic "
+                         "r_t = E[sign(D(real))], and the sign of an unbounded Wasserstein critic's output says nothing "
+                         "about overfitting; use a fixed augment_p (and augment_blit) instead" % expt)
 
 
 def check_swd_keys(run):
@@ -177,6 +222,9 @@ def compose(conf_dir, expt, overrides, run=None):
     """The experiment's config: from ``conf_dir`` when given, else from the built-in tree."""
     run = run or dict(RUNNER_KEYS)
     check_diffaugment(run)
+    for key in ADA_KEYS:
+        run.setdefault(key, RUNNER_KEYS[key])
+    check_ada_keys(run, expt)
     if conf_dir:
         from . import dropin
         dropin.install()
@@ -185,6 +233,8 @@ def compose(conf_dir, expt, overrides, run=None):
         except ConfigError as e:
             raise SystemExit("config error: %s" % e) from e
         cfg["diffaugment"] = run["diffaugment"]       # read by BaseGAN.__init__
+        for key in ADA_KEYS:
+            cfg[key] = run[key]
         return cfg
     dotted, dataset, filepaths = {}, "synthetic", {}
     for arg in overrides:
@@ -216,6 +266,8 @@ def compose(conf_dir, expt, overrides, run=None):
     cfg = make_cfg(expt, dotted=dotted)
     cfg["dataset"] = _to_cfg(_builtin_dataset(dataset, run, filepaths))
     cfg["diffaugment"] = run["diffaugment"]           # read by BaseGAN.__init__
+    for key in ADA_KEYS:                              # likewise (augment.build_augment)
+        cfg[key] = run[key]
     cfg.train["channels_img"] = cfg.dataset.get("n_channels", 3) if "train.channels_img" not in dotted else \
         cfg.train["channels_img"]
     return cfg
@@ -460,6 +512,9 @@ def checkpoint_blob(module, trainer, step, epoch, keeper=None, average=None):
             "callbacks": {}}
     if keeper is not None:
         blob["callbacks"]["ModelCheckpoint"] = keeper.state()
+    aug = getattr(module, "diffaugment", None)
+    if getattr(aug, "adaptive", False):       # the controller's p and its step count (rank 0's, restored to every rank)
+        blob["callbacks"]["AdaptiveAugment"] = aug.state_dict()
     return blob
 
 
@@ -486,6 +541,13 @@ def load_checkpoint(path, module, trainer, average=None, verbose=True):
             if verbose:
                 print("generator_average: %s holds no averaged weights; the average starts from the loaded generator"
                       % path)
+    aug = getattr(module, "diffaugment", None)
+    if getattr(aug, "adaptive", False):
+        saved = blob.get("callbacks", {}).get("AdaptiveAugment")
+        if saved:
+            aug.load_state_dict(saved)
+        elif verbose:
+            print("ada_target: %s holds no AdaptiveAugment state; p starts from %g" % (path, aug.p_start))
     for o, s in zip(trainer.optim, blob.get("optimizer_states", [])):
         o["optimizer"].load_state_dict(s)
     for o, s in zip(trainer.optim, blob.get("lr_schedulers", [])):
@@ -618,6 +680,12 @@ def fit(module, cfg, data, run, sync=None, rank=0, world=1, evaluate=None, slow_
         step += 1
         if step % run["log_every"] == 0 and rank == 0:
             msg = " ".join("%s=%.4f" % (k, float(v)) for k, v in sorted(last.items()))
+            aug = getattr(module, "diffaugment", None)
+            if getattr(aug, "adaptive", False):           # the one place the host reads the controller's state
+                ada_p, ada_r = aug.values()
+                module.log("train/ada_p", ada_p)
+                module.log("train/ada_r", ada_r)
+                msg += " ada_p=%.4f ada_r=%.4f" % (ada_p, ada_r)
             rate = (step - first_step) * t.batch_size * world / (time.time() - t0)
             print("step %d epoch %d %s (%.1f img/s)" % (step, epoch, msg, rate))
         if step % steps_per_epoch == 0:
